@@ -9,17 +9,23 @@ its SNV cone, bit-identical to per-window forwards) + the float64 fwd/rc mean an
 exp-decay reduction to 20030 features per allele (geuvadis_sed_for_top_eqtls.py:83-121).
 `value` is timed with layer profiling OFF; the f16x3 overflow flag is checked at the end of
 every step (the release point of a batch) and a flagged step is recomputed in bf16x6 inside
-the timed region.  Layer times and the roofline come from a separate profiled pass.
+the timed region.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 bench.py --gpus N
 
-N>1: weak scaling, each rank its own 96 variants per step, no collective in the step (variants
-are independent).  N>1 extra, outside `value`: configs[3]'s per-rank shape (100k SNVs over 8
-ranks = 12.5k SNVs x 9 shifts per rank) computed once and its outputs gathered to rank 0 per
-shift over RCCL (the file-output exchange), both timed.  Rank 0 prints ONE JSON line.
+A plain run sets up, warms up, times the K steps and prints the result line (the headline
+figure, `ms_per_step`, the workload's description); nothing else runs.  --dump-outputs DIR
+writes what the last timed step computed (DIR/features.npy, DIR/predictions.npy; dump_outputs).
+Everything below that takes runs of its own is behind --full: layer times and the roofline
+(a separate profiled pass), the N>1 extra, the N=1 extras and the CPU baseline.
 
-N=1 extras, outside `value`: the headline in bf16x6 (fp32-faithful split), configs[1]
+N>1: weak scaling, each rank its own 96 variants per step, no collective in the step (variants
+are independent).  N>1 extra (--full), outside `value`: configs[3]'s per-rank shape (100k SNVs
+over 8 ranks = 12.5k SNVs x 9 shifts per rank) computed once and its outputs gathered to rank 0
+per shift over RCCL (the file-output exchange), both timed.  Rank 0 prints ONE JSON line.
+
+N=1 extras (--full), outside `value`: the headline in bf16x6 (fp32-faithful split), configs[1]
 (1k SNVs, shift 0), configs[2] (+-800 sweep), configs[4] TSS genes, the chromatin CLI end to
 end (streamed batches vs one batch: compute overlapped with the .diff.h5 writes), the HBM-bound
 reductions in GB/s, and the CPU port timed on host cores (P = this job's CPU share and 8, batch 32 and 512).
@@ -279,8 +285,10 @@ class Sed200:
         self.y = [torch.empty((2, 2, n, S, 2002), dtype=torch.float32, device=dev) for _ in range(2)]
         self.w = torch.from_numpy(tss_pos_weights(np.asarray(SHIFTS_200))).to(dev)
         self.feat = [torch.empty((2, n, 20030), dtype=torch.float64, device=dev) for _ in range(2)]
+        self.last = 0                                  # the slot the latest step wrote (dump_outputs)
 
     def __call__(self, slot=0):
+        self.last = slot
         self.pipe.predict(self.prep, out=self.y[slot])
         self.pipe.sed_features(self.y[slot], self.w, out=self.feat[slot])
 
@@ -501,15 +509,43 @@ def layer_summary(layers, el_steps):
             {k: 2.0 * m / (ms * 1e-3) / 1e12 for k, (ms, c, m) in layers.items() if ms > 0})
 
 
-def measure(step, eng, n_units, steps, warmup, world, dev, prof_steps=2, segments=True):
-    """(units/s, ms/step, fallbacks, layers, roofline, executed MACs per step)."""
-    el, fb = time_steps(step, eng, steps, warmup, world, dev)
+def profiled(step, eng, prof_steps=2, segments=True):
+    """(layers, roofline, executed MACs per step) of a profiled pass of `prof_steps` steps."""
     layers = profile_layers(step, eng, prof_steps)
     main = main_launches(eng)
     exec_macs = sum(m for _, _, m in layers.values()) / prof_steps
-    return {"units_per_s": world * n_units * steps / el, "ms_per_step": el / steps * 1e3, "fallbacks": fb,
-            "layers": layers, "roofline": roofline(layers, eng.precision, segments, main), "exec_macs_step": exec_macs,
+    return {"layers": layers, "roofline": roofline(layers, eng.precision, segments, main), "exec_macs_step": exec_macs,
             "prof_steps": prof_steps}
+
+
+def measure(step, eng, n_units, steps, warmup, world, dev, prof_steps=2, segments=True):
+    """(units/s, ms/step, fallbacks, layers, roofline, executed MACs per step)."""
+    el, fb = time_steps(step, eng, steps, warmup, world, dev)
+    return {"units_per_s": world * n_units * steps / el, "ms_per_step": el / steps * 1e3, "fallbacks": fb,
+            **profiled(step, eng, prof_steps, segments)}
+
+
+DUMP_SEED = 20240                 # of the sample --dump-outputs takes of an array too large to write whole
+DUMP_MAX_ELEMS = {"features": 5_000_000, "predictions": 4_000_000}   # 40 MB float64 + 16 MB float32
+
+
+def dump_outputs(head, d, rank=0, world=1):
+    """--dump-outputs: what the caller of the headline step receives, from the last step run (its
+    output slot, released: a flagged step already recomputed), as DIR/<name>.npy:
+      features     float64 [2 alleles, n, 20030], the exp-decay features (sed_features);
+      predictions  float32, of y[2 strands, 2 alleles, n, 200 shifts, 2002] (predict).
+    An array of more than DUMP_MAX_ELEMS[name] elements is written as that many elements of the
+    flattened array at seeded positions (DUMP_SEED; sorted, the same from run to run), so a dump
+    stays under 64 MB.  Rank r of N > 1 writes <name>.rank<r>.npy.  Called after time_steps, whose
+    last act is a device-wide sync."""
+    os.makedirs(d, exist_ok=True)
+    sfx = "" if world == 1 else f".rank{rank}"
+    for name, t in (("features", head.feat[head.last]), ("predictions", head.y[head.last])):
+        cap = DUMP_MAX_ELEMS[name]
+        if t.numel() > cap:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, t.numel(), cap))
+            t = t.reshape(-1)[torch.from_numpy(idx).to(t.device)]
+        np.save(os.path.join(d, f"{name}{sfx}.npy"), t.cpu().numpy())
 
 
 def extra_record(m, unit, n_units, windows_per_unit, precision):
@@ -814,11 +850,16 @@ def main():
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--variants", type=int, default=N200, help="200-window variants per GPU per step")
-    ap.add_argument("--cpu-seconds", type=float, default=7.0, help="per CPU-baseline setting (4 settings)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the extra workloads")
-    ap.add_argument("--no-e2e", action="store_true", help="skip the hg19-sized CLI end-to-end extra")
-    ap.add_argument("--extras", default="all", help="comma-separated extra workloads to run (default all): "
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's outputs as DIR/<name>.npy (dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also run the profiled pass (layer times, roofline), the extra "
+                         "workloads, the CPU baseline and, on N>1, configs[3]'s per-rank shard")
+    ap.add_argument("--cpu-seconds", type=float, default=7.0, help="--full: per CPU-baseline setting (4 settings)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-extras", action="store_true", help="--full without the extra workloads")
+    ap.add_argument("--no-e2e", action="store_true", help="--full without the hg19-sized CLI end-to-end extra")
+    ap.add_argument("--extras", default="all", help="--full: comma-separated extra workloads to run (default all): "
                     "headline_other,cfg1,cfg2,cfg4,operator_api,cli_streamed,replicate_rank,cli_e2e,hbm")
     ap.add_argument("--precision", default=None, help="GEMM arithmetic (default: the engine default)")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL) for the scaling runs; gloo to "
@@ -837,7 +878,8 @@ def main():
     genome = synthetic.genome_bytes(n_contigs=24, contig_len=2_000_000, seed=0, repeats=True)
     fasta = Fasta.from_dict(genome)
     model = beluga.seeded(0, gain=math.sqrt(6.0), max_batch=MAX_BATCH)
-    sd_cpu = {k: v.detach().clone() for k, v in model.state_dict().items()} if (rank == 0 and world == 1) else None
+    cpu_base = args.full and rank == 0 and world == 1 and not args.no_cpu_baseline
+    sd_cpu = {k: v.detach().clone() for k, v in model.state_dict().items()} if cpu_base else None
     model = model.cuda()
     eng = model.engine()
     if args.precision:
@@ -846,22 +888,14 @@ def main():
     pipe = VariantPipeline(eng, fasta, DeviceGenome(fasta, device=dev))
     head = Sed200(pipe, genome, n, 202 + rank, dev)    # variant tables resident in HBM
 
-    m = measure(head, eng, n, args.steps, args.warmup, world, dev)
-    ms_l, tf_l = layer_summary(m["layers"], m["prof_steps"])
-    mult, peak = products_and_peak(eng.precision)
-    step_s = m["ms_per_step"] * 1e-3
+    el, fallbacks = time_steps(head, eng, args.steps, args.warmup, world, dev)
+    if args.dump_outputs:
+        dump_outputs(head, args.dump_outputs, rank, world)
+    units_per_s = world * n * args.steps / el
     key = profile_key(n, eng.precision)
-    roof = m["roofline"]
-    roof["traffic"], src = pmc_traffic(key, roof["kernel"])
-    if roof["traffic"] is not None:
-        roof["traffic_unit"] = "bytes/launch (HBM read+write)"
-        roof["traffic_source"] = src
-    held = pmc_held_clock(key, roof["kernel"])
-    if held is not None:
-        roof["pmc"] = held
     rec = {
-        "metric": METRIC, "value": m["units_per_s"], "unit": "variants/s", "n_gpus": world, "steps": args.steps,
-        "warmup": args.warmup, "ms_per_step": m["ms_per_step"], "higher_is_better": True, "scaling": "weak",
+        "metric": METRIC, "value": units_per_s, "unit": "variants/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": el / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
         "vs_baseline": None,
         "dtype": DTYPES[eng.precision],
         "data": "synthetic: seeded repeat-rich genome (24 x 2 Mbp: ~45 % soft-masked homopolymer / tandem / "
@@ -872,27 +906,42 @@ def main():
                                f"reduction to 20030 features per allele (geuvadis_sed_for_top_eqtls.py:61-121)",
                    "variants_per_gpu_step": n, "windows_per_variant": WIN_PER_VARIANT_200,
                    "parallelism": f"dp{world} (variant shards)"},
-        "windows_per_s": m["units_per_s"] * WIN_PER_VARIANT_200,
-        "dense_equivalent_tflops": 2.0 * WINDOW_MACS * m["units_per_s"] * WIN_PER_VARIANT_200 / 1e12,
-        "executed_fp32_tflops": 2.0 * m["exec_macs_step"] * world / step_s / 1e12,
-        "step_mfma_frac": mult * 2.0 * m["exec_macs_step"] / step_s / 1e12 / peak,
-        "roofline": roof,
-        "conv2_table_gather": (conv2_table_roofline(m["layers"], n)
-                               if conv2_table_on(eng.precision) else None),
-        "layer_ms_per_step": ms_l,
-        "layer_tflops": tf_l,
-        "layer_timing": f"separate profiled pass of {m['prof_steps']} steps (HIP events per launch); the "
-                        f"*_delta slots run on the second stream beside the ref launches (upper bounds)",
-        "f16_fallback_steps": m["fallbacks"],
+        "windows_per_s": units_per_s * WIN_PER_VARIANT_200,
+        "dense_equivalent_tflops": 2.0 * WINDOW_MACS * units_per_s * WIN_PER_VARIANT_200 / 1e12,
+        "f16_fallback_steps": fallbacks,
         "conv2_table": dict(zip(("active", "state"), eng.conv2_table_state())),
         "profile_key": key,
         "reuse": "segments (conv trunk shared by the 200 shifts) + alt-cone (the alt allele recomputes only the "
                  "rows its SNV changes; windows without it copy the ref row); bit-identical to per-window forwards",
     }
+    if args.full:   # layer times and the roofline: a profiled pass of its own, after the timed steps
+        m = profiled(head, eng)
+        ms_l, tf_l = layer_summary(m["layers"], m["prof_steps"])
+        mult, peak = products_and_peak(eng.precision)
+        step_s = rec["ms_per_step"] * 1e-3
+        roof = m["roofline"]
+        roof["traffic"], src = pmc_traffic(key, roof["kernel"])
+        if roof["traffic"] is not None:
+            roof["traffic_unit"] = "bytes/launch (HBM read+write)"
+            roof["traffic_source"] = src
+        held = pmc_held_clock(key, roof["kernel"])
+        if held is not None:
+            roof["pmc"] = held
+        rec.update({
+            "executed_fp32_tflops": 2.0 * m["exec_macs_step"] * world / step_s / 1e12,
+            "step_mfma_frac": mult * 2.0 * m["exec_macs_step"] / step_s / 1e12 / peak,
+            "roofline": roof,
+            "conv2_table_gather": (conv2_table_roofline(m["layers"], n)
+                                   if conv2_table_on(eng.precision) else None),
+            "layer_ms_per_step": ms_l,
+            "layer_tflops": tf_l,
+            "layer_timing": f"separate profiled pass of {m['prof_steps']} steps (HIP events per launch); the "
+                            f"*_delta slots run on the second stream beside the ref launches (upper bounds)",
+        })
     if eng.precision == "f16x3":
         fb, sx = eng.f16_state()
         rec["f16x3"] = {"fallback_calls": fb, "activation_scale_exp": sx}
-    if world == 1 and not args.no_extras:
+    if args.full and world == 1 and not args.no_extras:
         extras = {}
         want = set(args.extras.split(",")) if args.extras != "all" else None
         run = lambda name: want is None or name in want   # noqa: E731
@@ -924,7 +973,7 @@ def main():
         if run("hbm"):
             extras["hbm_reductions"] = hbm_reductions(dev)
         rec["extra_workloads"] = extras
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if cpu_base:
         from expecto_amd.encode import seqs_to_codes
         rng = np.random.default_rng(5)
         sample = []
@@ -934,7 +983,7 @@ def main():
             sample.append(genome[c][p - 1000:p + 1000].decode())
         rec["cpu_baseline"] = cpu_baseline(sd_cpu, seqs_to_codes(sample), args.cpu_seconds, WIN_PER_VARIANT_200)
         rec["speedup_vs_cpu_baseline"] = rec["value"] / rec["cpu_baseline"]["value"]
-    if world > 1:
+    if args.full and world > 1:
         rec["cfg3_rank_shard"] = cfg3_rank_shard(pipe, eng, genome, rank, world, dev)
     if rank == 0:
         print(json.dumps(rec))

@@ -50,6 +50,32 @@ def test_committed_sq_counters_give_the_held_clock():
     assert 0.3 < held["mfma_busy"] <= 1.0 and 1.0 < held["held_clock_ghz"] < 2.6
 
 
+def test_dump_outputs_writes_whole_or_seeded_sample(tmp_path):
+    """--dump-outputs: the last slot's arrays as float64 / float32 .npy, whole when small, else a
+    fixed number of elements at seeded positions, identical from call to call; under 64 MB in all
+    at the headline's shapes."""
+    import types
+    import numpy as np
+    import torch
+    import bench
+    n = 3
+    feat = [torch.zeros((2, n, 20030), dtype=torch.float64), torch.rand((2, n, 20030), dtype=torch.float64)]
+    y = [torch.zeros((2, 2, n, 200, 2002)), torch.rand((2, 2, n, 200, 2002))]
+    head = types.SimpleNamespace(feat=feat, y=y, last=1)
+    bench.dump_outputs(head, str(tmp_path / "a"))
+    bench.dump_outputs(head, str(tmp_path / "b"), rank=1, world=2)
+    f, p = np.load(tmp_path / "a" / "features.npy"), np.load(tmp_path / "a" / "predictions.npy")
+    assert f.dtype == np.float64 and np.array_equal(f, feat[1].numpy())          # small: whole
+    cap = bench.DUMP_MAX_ELEMS["predictions"]
+    assert p.dtype == np.float32 and p.shape == (cap,) and y[1].numel() > cap    # large: sampled
+    idx = np.sort(np.random.default_rng(bench.DUMP_SEED).integers(0, y[1].numel(), cap))
+    assert np.array_equal(p, y[1].reshape(-1).numpy()[idx])
+    assert np.array_equal(p, np.load(tmp_path / "b" / "predictions.rank1.npy"))
+    full = 2 * bench.N200 * 20030                       # the headline's features are written whole
+    assert full <= bench.DUMP_MAX_ELEMS["features"]
+    assert 8 * bench.DUMP_MAX_ELEMS["features"] + 4 * cap + 256 <= 64e6
+
+
 def test_cpu_baseline_share_is_this_jobs_cpus():
     """cpu_baseline's P is the job's CPU share (affinity mask, cgroup quota), not os.cpu_count()
     of the whole machine."""

@@ -3,7 +3,7 @@
 #
 #   tests    pytest -m gpu (one process, per-test time limit)
 #   smoke    __graft_entry__.smoke()
-#   bench    python bench.py (default K/W; extras + cpu_baseline)           -> gpurun_out/bench.log
+#   bench    python bench.py --full (default K/W; extras + cpu_baseline)    -> $OUT/bench.log
 #   prof     rocprofv3 --kernel-trace --stats of the headline               -> gpurun_out/prof_$TAG/
 #   pmc      FETCH_SIZE, WRITE_SIZE and SQ busy counters, one --pmc pass each (same command)
 #   power    rocm-smi power / clock samples during 200 headline steps       -> gpurun_out/power.log
@@ -41,7 +41,7 @@ cd $REPO
 B="python3 $REPO/bench.py --no-extras --no-cpu-baseline"
 has tests && run gpu_tests 1500 python -u -m pytest tests -m gpu -x -q --timeout 300 --timeout-method thread
 has smoke && run smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
-has bench && run bench 900 python -u bench.py
+has bench && run bench 900 python -u bench.py --full
 if has prof; then
   run prof_$TAG 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof_$TAG -o run -- $B --steps 5 --warmup 2
 fi
