@@ -69,6 +69,14 @@ SIGNATURES = {
                                                   c_vp, ctypes.c_int, c_vp, c_vp]),
     "expecto_gblinear_predict": (ctypes.c_int, [c_vp, ctypes.c_longlong, ctypes.c_longlong, c_vp, ctypes.c_int,
                                                 c_vp, ctypes.c_float, c_vp, c_vp]),
+    "expecto_gblinear_train_round": (ctypes.c_int, [c_vp, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                    c_vp, ctypes.c_longlong, c_vp, ctypes.c_longlong, c_vp, c_vp,
+                                                    ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
+                                                    ctypes.c_double, ctypes.c_float, c_vp, c_vp]),
+    "expecto_gblinear_predict_cols": (ctypes.c_int, [c_vp, ctypes.c_longlong, ctypes.c_int, ctypes.c_int,
+                                                     ctypes.c_int, c_vp, ctypes.c_float, c_vp, c_vp]),
+    "expecto_gblinear_rmse": (ctypes.c_int, [c_vp, c_vp, ctypes.c_longlong, c_vp, ctypes.c_longlong, ctypes.c_int,
+                                             ctypes.c_int, c_vp, c_vp]),
     "expecto_shift_reduce": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                             c_vp, c_vp]),
     "expecto_last_error": (ctypes.c_char_p, []),

@@ -1,0 +1,186 @@
+"""Drop-in for the reference ``train.py`` / ``train_bootstrap.py`` CLIs: TSS features
+(``Xreducedall*.npy``) and an expression table -> ExPecto gblinear models, trained on the GPU.
+
+    python -m expecto_amd.train --expFile geneanno.exp.csv --targetIndex 1 \\
+        --belugaFeatures features.tsv --inputFile Xreducedall.2002.npy --output_dir models
+
+Same arguments and defaults as ``train.py:27-77``, the same row selection (``train.py:86-100``,
+``:127-138``: train = every gene off chrX, chrY and chr8, test = chr8, both under the
+``--filterStr`` filter and the finite-log filter), the same ``Cell type:`` / ``Training data
+shape:`` / ``[i]\\teval-rmse:%f\\ttrain-rmse:%f`` / Spearman lines and the same ``.save`` /
+``.dump`` file names (``train.py:156-159``).  ``xgb.train`` is replaced by
+:func:`expecto_amd.xgblinear.train` (xgboost is not needed); ``--threads`` is accepted and
+ignored (the single-thread update order is the definition).
+
+Additions: ``--targetIndex`` takes several column indices or ``all`` (every column but the
+first); targets with the same row selection are trained as one batch on one device copy of the
+features.  ``--n_bootstrap K --seed S`` folds in ``train_bootstrap.py``: replicate k draws
+``np.random.RandomState(S + k).choice(trainind, trainind.size, replace=True)`` (replicate 0 is
+the draw of ``train_bootstrap.py --seed S``) and trains on the draw counts as row weights, not
+on a gathered copy; its files carry ``.boot{k}`` ahead of the extension.  ``--l1`` is passed on
+as ``alpha`` (the reference parses it and then trains with ``alpha: 0``; the default is 0).
+
+Left out: the scatter plots (``train.py:161-184``), ``--kidney_genes_only`` and
+``--match_with_basenji2`` (the latter reads a hard-coded path of its author's machine).
+``--annoFile`` is honoured (the reference parses it and reads ``./resources/geneanno.csv``,
+its default, regardless).
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import sys
+
+import numpy as np
+import pandas as pd
+
+from .predict import NFEAT, get_keep_mask
+from .xgblinear import ColMatrix, predict_cols, train
+
+
+def build_parser():
+    p = argparse.ArgumentParser(description='Process some integers.')
+    p.add_argument('--targetIndex', action="store", dest="targetIndex", nargs='+', required=True,
+                   help="column(s) of expFile to train on, or 'all'")
+    p.add_argument('--expFile', action="store", dest="expFile")
+    p.add_argument('--belugaFeatures', action="store", dest="belugaFeatures", help="tsv file denoting Beluga features")
+    p.add_argument('--inputFile', action="store", dest="inputFile", default='./resources/Xreducedall.2002.npy')
+    p.add_argument('--annoFile', action="store", dest="annoFile", default='./resources/geneanno.csv')
+    p.add_argument('--evalFile', action="store", dest="evalFile", default='',
+                   help='specify to save holdout set predictions')
+    p.add_argument('--filterStr', action="store", dest="filterStr", type=str, default="all")
+    p.add_argument('--pseudocount', action="store", dest="pseudocount", type=float, default=0.0001)
+    p.add_argument('--num_round', action="store", dest="num_round", type=int, default=100)
+    p.add_argument('--l2', action="store", dest="l2", type=float, default=100)
+    p.add_argument('--l1', action="store", dest="l1", type=float, default=0)
+    p.add_argument('--eta', action="store", dest="eta", type=float, default=0.01)
+    p.add_argument('--base_score', action="store", dest="base_score", type=float, default=2)
+    p.add_argument('--threads', action="store", dest="threads", type=int, default=16, help="accepted and ignored")
+    p.add_argument('--no_tf_features', action='store_true', dest='no_tf_features', default=False)
+    p.add_argument('--no_dnase_features', action='store_true', dest='no_dnase_features', default=False)
+    p.add_argument('--no_histone_features', action='store_true', dest='no_histone_features', default=False)
+    p.add_argument('--intersect_with_lambert', action='store_true', dest='intersect_with_lambert', default=False)
+    p.add_argument('--no_pol2', action='store_true', dest='no_pol2', default=False)
+    p.add_argument('--output_dir', type=str, default='temp_expecto_model')
+    p.add_argument('--n_bootstrap', type=int, default=0, help="bootstrap replicates per target (0: none)")
+    p.add_argument('--seed', action="store", dest="seed", type=int, default=0)
+    return p
+
+
+def gene_filter(geneanno: pd.DataFrame, filter_str: str) -> np.ndarray:
+    """train.py:86-93."""
+    if filter_str == 'pc':
+        return np.asarray(geneanno.iloc[:, -1] == 'protein_coding')
+    if filter_str == 'lincRNA':
+        return np.asarray(geneanno.iloc[:, -1] == 'lincRNA')
+    if filter_str == 'all':
+        return np.asarray(geneanno.iloc[:, -1] != 'rRNA')
+    raise ValueError('filterStr has to be one of all, pc, and lincRNA')
+
+
+def select_rows(geneanno: pd.DataFrame, expr: pd.Series, filter_str: str, pseudocount: float):
+    """Boolean (train, test) masks over the genes for one expression column (train.py:86-100,
+    :127-132)."""
+    with np.errstate(divide='ignore', invalid='ignore'):
+        filt = gene_filter(geneanno, filter_str) * np.isfinite(np.asarray(np.log(expr + pseudocount)))
+    trainind = np.asarray(geneanno['seqnames'] != 'chrX') * np.asarray(
+        geneanno['seqnames'] != 'chrY') * np.asarray(geneanno['seqnames'] != 'chr8')
+    testind = np.asarray(geneanno['seqnames'] == 'chr8')
+    return np.asarray(trainind * filt, dtype=bool), np.asarray(testind * filt, dtype=bool)
+
+
+def bootstrap_weights(train_mask: np.ndarray, seed: int) -> np.ndarray:
+    """Draw counts per gene of train_bootstrap.py:88-90 under ``np.random.seed(seed)``: training on
+    rows ``choice(trainind, size, replace=True)`` is training on every row with its count as weight."""
+    trainind = np.where(train_mask)[0]
+    draw = np.random.RandomState(seed).choice(trainind, size=trainind.shape[0], replace=True)
+    return np.bincount(draw, minlength=train_mask.shape[0])
+
+
+def target_indices(spec, ncols: int) -> list:
+    if len(spec) == 1 and spec[0] == 'all':
+        return list(range(1, ncols))
+    return [int(s) for s in spec]
+
+
+def spearman_line(ypred, ytrue) -> str:
+    try:
+        from scipy.stats import spearmanr
+        return str(spearmanr(ypred, ytrue))
+    except ImportError:
+        rho = np.corrcoef(pd.Series(ypred).rank(), pd.Series(ytrue).rank())[0, 1]
+        return f"SignificanceResult(statistic={rho}, pvalue=nan)"
+
+
+def run(args) -> list:
+    """Train every requested model; returns one dict per model (name, boot, model, history,
+    save, dump) in the order their lines were printed."""
+    os.makedirs(args.output_dir, exist_ok=True)
+    X = np.load(args.inputFile)
+    geneanno = pd.read_csv(args.annoFile)
+    geneexp = pd.read_csv(args.expFile)
+    targets = target_indices(args.targetIndex, geneexp.shape[1])
+
+    beluga_features_df = pd.read_csv(args.belugaFeatures, sep='\t', index_col=0)
+    beluga_features_df['Assay type + assay + cell type'] = (beluga_features_df['Assay type'] + '/' +
+                                                           beluga_features_df['Assay'] + '/' +
+                                                           beluga_features_df['Cell type'])
+    keep_mask = get_keep_mask(beluga_features_df, args.no_tf_features, args.no_dnase_features,
+                              args.no_histone_features, args.intersect_with_lambert, args.no_pol2)
+    keep_indices = np.nonzero(keep_mask)[0]
+    num_genes = X.shape[0]
+    X = X.reshape(num_genes, 10, NFEAT)[:, :, keep_indices].reshape(num_genes, -1)
+    print(f'Training data shape: {X.shape}')
+
+    # targets with the same row selection share one device copy of the features and one batch
+    groups = {}
+    for ti in targets:
+        tr, te = select_rows(geneanno, geneexp.iloc[:, ti], args.filterStr, args.pseudocount)
+        groups.setdefault((tr.tobytes(), te.tobytes()), (tr, te, []))[2].append(ti)
+
+    results = []
+    for tr, te, tis in groups.values():
+        Xtr, Xte = ColMatrix(X[tr]), ColMatrix(X[te])
+        jobs = []                                      # (target, replicate or None, y_train, weight, y_test)
+        for ti in tis:
+            ylog = np.asarray(np.log(geneexp.iloc[:, ti] + args.pseudocount))
+            reps = [None] if args.n_bootstrap <= 0 else list(range(args.n_bootstrap))
+            for k in reps:
+                wgt = np.ones(int(tr.sum())) if k is None else bootstrap_weights(tr, args.seed + k)[tr]
+                jobs.append((ti, k, ylog[tr], wgt, ylog[te]))
+        ytr = np.stack([j[2] for j in jobs])
+        wtr = np.stack([j[3] for j in jobs]) if args.n_bootstrap > 0 else None
+        yte = np.stack([j[4] for j in jobs])
+        models, history = train(Xtr, ytr, wtr, num_round=args.num_round, eta=args.eta, lambda_=args.l2,
+                                alpha=args.l1, base_score=args.base_score, evals=[(Xte, yte)])
+        ypred = predict_cols(Xte, models).cpu().numpy()
+        for m, (ti, k, _, _, ytrue) in enumerate(jobs):
+            name = geneexp.columns[ti]
+            print(f"Cell type: {name}" + ("" if k is None else f" (bootstrap {k})"))
+            for r in range(args.num_round):
+                print("[%d]\teval-rmse:%f\ttrain-rmse:%f" % (r, history[m, r, 1], history[m, r, 0]))
+            print(spearman_line(ypred[m], ytrue))
+            tag = "" if k is None else f".boot{k}"
+            if args.evalFile != '':
+                path = args.evalFile if len(jobs) == 1 and len(groups) == 1 else f"{args.evalFile}.{name}{tag}"
+                pd.DataFrame({'pred': ypred[m], 'target': ytrue}).to_csv(path)
+            stem = (f'{args.output_dir}/expecto_{args.filterStr}.pseudocount{args.pseudocount}.lambda{args.l2}'
+                    f'.round{args.num_round}.basescore{args.base_score}.{name}{tag}')
+            models[m].save_legacy(stem + '.save')
+            models[m].save_dump(stem + '.dump')
+            results.append({"name": name, "boot": k, "model": models[m], "history": history[m],
+                            "save": stem + '.save', "dump": stem + '.dump'})
+    return results
+
+
+def main(argv=None):
+    import torch
+
+    args = build_parser().parse_args(argv)
+    if not torch.cuda.is_available():
+        raise RuntimeError("expecto_amd.train needs a GPU (HIP); there is no CPU path")
+    return run(args)
+
+
+if __name__ == "__main__":
+    main(sys.argv[1:])

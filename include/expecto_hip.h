@@ -29,6 +29,10 @@
  *   expecto_tss_reduce             pos_weights x pred_fwd_rc (compute_expecto_features.py:91-124)
  *   expecto_variant_reduce(_lut)   exp-decay shift weights x effects (predict.py:87-136)
  *   expecto_gblinear_predict       xgboost gblinear scoring of feature rows (predict.py:150-166)
+ *   expecto_gblinear_train_round   one xgb.train boosting round of gblinear / reg:linear models
+ *                                  (train.py:140-146, train_bootstrap.py:88-106)
+ *   expecto_gblinear_predict_cols  bst.predict(dtrain / dtest) on the training matrix (train.py:147)
+ *   expecto_gblinear_rmse          the eval-rmse / train-rmse of xgb.train's evallist (train.py:144-146)
  *   expecto_shift_reduce           200-shift reduction of consensus / eQTL sequences
  *                                  (geuvadis_sed_for_top_eqtls.py:95-121, geuvadis_predict_consensus.py:110-128)
  *   expecto_beluga_destroy         (model teardown)
@@ -311,6 +315,40 @@ int expecto_shift_reduce(const float* fwd, const float* rc, const double* weight
  * (the keep-mask column map of predict.py:137-145), w: float32[ncols]. */
 int expecto_gblinear_predict(const double* X, long long n, long long ld, const int* cols, int ncols, const float* w,
                              float init, float* out, void* stream);
+
+/* Training of gblinear / reg:linear models (xgboost 0.7 GBLinear::DoBoost with nthread=1, the
+ * arithmetic of DESIGN.md "Training gblinear models"): cyclic coordinate descent, float32 state,
+ * double sums over rows in a fixed order, no atomics -- a model's bits do not depend on the batch
+ * it is trained in.  X is the float32 feature matrix held COLUMN-major, feature j at X + j*ld
+ * (ld >= n), shared by the n_models models of a call; model m has labels y + m*y_stride, row
+ * weights h + m*h_stride (h NULL = ones; a stride of 0 shares one vector: a bootstrap replicate
+ * is its draw counts as h), weights w + m*(num_feature+1) with the bias last (the .save order)
+ * and the workspace sh + m*num_feature.  All pointers are DEVICE memory.
+ *
+ * One call is one boosting round of every model: predict, gradient, bias step, then one pass
+ * over the features in order, updating w in place (zero w before the first round).  first != 0:
+ * the call also computes every feature's hessian sum into sh; later rounds (first = 0, same X and
+ * h) read it.  pred (may be NULL): [n_models, n], receives the predictions the round STARTED
+ * from, i.e. those of the weights the previous round left.  One workgroup holds a model's
+ * gradient and row weights on chip for the whole pass: n <= EXPECTO_GBLINEAR_TRAIN_MAX_ROWS
+ * (EXPECTO_EINVAL above it; geneanno.csv has 24,338 genes). */
+#define EXPECTO_GBLINEAR_TRAIN_MAX_ROWS 24576
+int expecto_gblinear_train_round(const float* X, long long ld, int n, int num_feature, int n_models, const float* y,
+                                 long long y_stride, const float* h, long long h_stride, float* w, double* sh,
+                                 int first, double eta, double lambda, double alpha, double lambda_bias,
+                                 float base_score, float* pred, void* stream);
+
+/* out[m, i] = float32(bias_m + base_score) + sum_j X[j*ld + i] * w_m[j], in float32 in column
+ * order with every product and sum rounded separately (expecto_gblinear_predict's rule on the
+ * column-major float32 matrix); w as above, out [n_models, n].  n_models <= 65535. */
+int expecto_gblinear_predict_cols(const float* X, long long ld, int n, int num_feature, int n_models, const float* w,
+                                  float base_score, float* out, void* stream);
+
+/* out[m] = sqrt(sum_i h_i * (y_i - pred[m, i])^2 / sum_i h_i) (xgboost's rmse: the square and its
+ * product with h in float32, both sums in double); pred [n_models, n], y / h and their strides as
+ * above, out float64[n_models]. */
+int expecto_gblinear_rmse(const float* pred, const float* y, long long y_stride, const float* h, long long h_stride,
+                          int n, int n_models, double* out, void* stream);
 
 const char* expecto_last_error(void);
 const char* expecto_version(void);
