@@ -454,21 +454,32 @@ __global__ __launch_bounds__(256) void pool4_phases_h2m(const float* __restrict_
   }
 }
 
+// Strands of a segment call.  Its chunks run over (strand, segment) entries e, the fwd entries first:
+// entry e is segment e - n_seg if e >= n_seg, else e, on the rc strand iff e >= rc_ent.  Its windows
+// are numbered the same way: v is window v - n_win if v >= n_win (its rows then rc_rows further
+// on in the output), else v, on the rc strand iff v >= rc_win.  (FWD: rc_* past every index; RC: 0;
+// BOTH: n_seg / n_win.)
+struct SegStrands {
+  int n_seg, rc_ent, n_win, rc_win;
+  long long rc_rows;
+};
+
 // FC1 row table of the windows of one segment chunk: window m of the chunk reads conv6
-// rows [off6, off6+106) of block (segment, pool2 phase).
-// (widx: optional list of window indices; row m then serves window widx[m].)
+// rows [off6, off6+106) of block (entry - ent_base, pool2 phase).
+// (widx: optional list of window numbers; row m then serves window widx[m].)
 __global__ void seg_a_rows(const int* __restrict__ win_seg, const int* __restrict__ win_off,
                            const int* __restrict__ win_row, const int* __restrict__ widx, int w0, int m_count,
-                           int seg_base, int rc, int seg_len, int n_ph, int4 ph_idx, int s7, long long row_base,
+                           int ent_base, SegStrands ss, int seg_len, int n_ph, int4 ph_idx, int s7,
                            long long* __restrict__ a_rows, long long* __restrict__ c_rows) {
   const int m = blockIdx.x * blockDim.x + threadIdx.x;
   if (m >= m_count) return;
-  const int w = widx ? widx[m] : w0 + m;
-  c_rows[m] = row_base + (win_row ? win_row[w] : w);
-  const int o = rc ? seg_len - 2000 - win_off[w] : win_off[w];
+  const int v = widx ? widx[m] : w0 + m;
+  const int sd = v >= ss.n_win ? 1 : 0, w = v - sd * ss.n_win;
+  c_rows[m] = sd * ss.rc_rows + (win_row ? win_row[w] : w);
+  const int o = v >= ss.rc_win ? seg_len - 2000 - win_off[w] : win_off[w];
   const int q = o >> 2, p = q & 3, off6 = (q - p) >> 2;
   const int pi = p == 0 ? ph_idx.x : p == 1 ? ph_idx.y : p == 2 ? ph_idx.z : ph_idx.w;
-  const long long blk = (long long)(win_seg[w] - seg_base) * n_ph + pi;
+  const long long blk = (long long)(win_seg[w] + sd * ss.n_seg - ent_base) * n_ph + pi;
   a_rows[m] = (blk * s7 + off6) * 640;
 }
 
@@ -621,12 +632,14 @@ struct SegDims {
   int L, T1, P1, T3, T4, S5, T5, T6;
 };
 
-__global__ void seg_delta_table(const int* __restrict__ var_pos, int s0, int ns, int rc, SegDims g, int n_ph, int4 ph,
-                                int* __restrict__ tab) {
+// (block m of the chunk = entry e0 + m, SegStrands)
+__global__ void seg_delta_table(const int* __restrict__ var_pos, int e0, int ns, SegStrands ss, SegDims g, int n_ph,
+                                int4 ph, int* __restrict__ tab) {
   const int m = blockIdx.x * blockDim.x + threadIdx.x;
   if (m >= ns) return;
-  int q = min(max(var_pos[s0 + m], 0), g.L - 1);
-  if (rc) q = g.L - 1 - q;
+  const int e = e0 + m;
+  int q = min(max(var_pos[e >= ss.n_seg ? e - ss.n_seg : e], 0), g.L - 1);
+  if (e >= ss.rc_ent) q = g.L - 1 - q;
   int* t = tab + m * kSegTab;
   const int r1 = clampi(q - 7, 0, g.T1 - kDW[1]);
   const int r2 = clampi(floor4(r1 - 7), 0, g.P1 - kDW[2]);
@@ -650,12 +663,15 @@ __global__ void seg_delta_table(const int* __restrict__ var_pos, int s0, int ns,
 
 // 16 codes from r1 of the alt segment, in the strand's orientation (rc: mirrored, complemented)
 __global__ void seg_delta_codes(const uint8_t* __restrict__ codes, long long stride, const uint8_t* __restrict__ alt_code,
-                                int s0, int ns, int rc, int L, const int* __restrict__ tab, uint8_t* __restrict__ out) {
+                                int e0, int ns, SegStrands ss, int L, const int* __restrict__ tab,
+                                uint8_t* __restrict__ out) {
   const int i = threadIdx.x & 15;
   const int m = blockIdx.x * (blockDim.x >> 4) + (threadIdx.x >> 4);
   if (m >= ns) return;
+  const int e = e0 + m, sg = e >= ss.n_seg ? e - ss.n_seg : e;
+  const bool rc = e >= ss.rc_ent;
   const int q = tab[m * kSegTab], x = min(tab[m * kSegTab + 1] + i, L - 1);
-  uint8_t c = x == q ? alt_code[s0 + m] : codes[(long long)(s0 + m) * stride + (rc ? L - 1 - x : x)];
+  uint8_t c = x == q ? alt_code[sg] : codes[(long long)sg * stride + (rc ? L - 1 - x : x)];
   if (rc && c < 4) c = (uint8_t)(3 - c);
   out[(long long)m * 16 + i] = c;
 }
@@ -668,14 +684,17 @@ __global__ void seg_delta_codes(const uint8_t* __restrict__ codes, long long str
 // delta_codes2 for the pair path's alt windows (as delta_codes).
 constexpr int kC1Pat = kDA[2] + 7, kC1PatStride = 48;
 __global__ void seg_delta_codes2(const uint8_t* __restrict__ codes, long long stride, const uint8_t* __restrict__ alt_code,
-                                 int s0, int ns, int rc, int L, const int* __restrict__ tab, uint8_t* __restrict__ out) {
+                                 int e0, int ns, SegStrands ss, int L, const int* __restrict__ tab,
+                                 uint8_t* __restrict__ out) {
   const int i = threadIdx.x % kC1PatStride;
   const int m = blockIdx.x * (blockDim.x / kC1PatStride) + threadIdx.x / kC1PatStride;
   if (m >= ns) return;
+  const int e = e0 + m, sg = e >= ss.n_seg ? e - ss.n_seg : e;
+  const bool rc = e >= ss.rc_ent;
   const int q = tab[m * kSegTab], x = 4 * tab[m * kSegTab + 2] + i;
   uint8_t c = 4;
   if (i < kC1Pat && x < L) {
-    c = x == q ? alt_code[s0 + m] : codes[(long long)(s0 + m) * stride + (rc ? L - 1 - x : x)];
+    c = x == q ? alt_code[sg] : codes[(long long)sg * stride + (rc ? L - 1 - x : x)];
     if (rc && c < 4) c = (uint8_t)(3 - c);
   }
   out[(long long)m * kC1PatStride + i] = c;
@@ -820,15 +839,17 @@ __global__ void seg_alt_blocks(const float* __restrict__ ref6, const float* __re
 // phase), whose alt run replaced block rows [r6, r6+20) (seg_delta_table), so its FC1 K range
 // that changed is 640 x that intersection.
 __global__ void fc1_slab_mask_seg(const int* __restrict__ widx, int n_alt, const int* __restrict__ win_seg,
-                                  const int* __restrict__ win_off, int seg_base, int rc, int seg_len, int4 ph_idx,
-                                  const int* __restrict__ tab, int tile_rows, int slab_k, unsigned* __restrict__ mask) {
+                                  const int* __restrict__ win_off, int ent_base, SegStrands ss, int seg_len,
+                                  int4 ph_idx, const int* __restrict__ tab, int tile_rows, int slab_k,
+                                  unsigned* __restrict__ mask) {
   const int m = blockIdx.x * blockDim.x + threadIdx.x;
   if (m >= n_alt) return;
-  const int w = widx[m];
-  const int o = rc ? seg_len - 2000 - win_off[w] : win_off[w];
+  const int v = widx[m];
+  const int sd = v >= ss.n_win ? 1 : 0, w = v - sd * ss.n_win;
+  const int o = v >= ss.rc_win ? seg_len - 2000 - win_off[w] : win_off[w];
   const int q = o >> 2, p = q & 3, off6 = (q - p) >> 2;
   const int pi = p == 0 ? ph_idx.x : p == 1 ? ph_idx.y : p == 2 ? ph_idx.z : ph_idx.w;
-  const int r6 = tab[(win_seg[w] - seg_base) * kSegTab + 13 + pi];
+  const int r6 = tab[(win_seg[w] + sd * ss.n_seg - ent_base) * kSegTab + 13 + pi];
   const int lo = max(r6 - off6, 0), hi = min(r6 + kDW[6] - off6, 106);
   if (lo >= hi) return;
   unsigned bits = 0;
@@ -838,9 +859,10 @@ __global__ void fc1_slab_mask_seg(const int* __restrict__ widx, int n_alt, const
 
 // y_alt rows of windows whose alt sequence equals the ref one (the SNV lies outside them)
 __global__ void copy_rows(const float* __restrict__ src, float* __restrict__ dst, const int* __restrict__ widx,
-                          const int* __restrict__ win_row, long long row_base) {
-  const int w = widx[blockIdx.x];
-  const long long r = (row_base + (win_row ? win_row[w] : w)) * kNFeat;
+                          const int* __restrict__ win_row, int n_win, long long rc_rows) {
+  const int v = widx[blockIdx.x];
+  const int sd = v >= n_win ? 1 : 0, w = v - sd * n_win;
+  const long long r = (sd * rc_rows + (win_row ? win_row[w] : w)) * kNFeat;
   for (int i = threadIdx.x; i < kNFeat; i += blockDim.x) dst[r + i] = src[r + i];
 }
 
@@ -1580,7 +1602,7 @@ struct expecto_beluga {
   int seg_var_cap = 0;
   int* win_off_d = nullptr;
   int* win_row_d = nullptr;
-  int* fc_perm_d = nullptr;      // segment pairs: FC row order per strand (2 x win_cap)
+  int* fc_perm_d = nullptr;      // segment pairs: FC row order of both strands' windows (4 x win_cap)
   hipStream_t st2 = nullptr;     // pair path: alt-delta launches overlap the ref launches
   hipEvent_t pev[16] = {};       //   (ordering events, no timing)
   bool overlap = true;           //   EXPECTO_OVERLAP=0: one stream (same bits either way)
@@ -1608,6 +1630,7 @@ struct expecto_beluga {
   int conv_narrow = -1;               // conv5 / conv6 tile width: -1 auto (conv_narrow), 0 160, 1 64 columns
   bool narrow_scope = false;          // inside forward_chunk: auto narrow tiles allowed (nothing runs beside)
   int seg_chunk_windows = 0;          // segment path: windows per chunk cap (0 = none; tuning knob)
+  bool seg_merge_strands = true;      // segment path: a chunk may hold entries of both strands (EXPECTO_SEG_MERGE_STRANDS)
   int cus = 0;                        // compute units of the device (workgroups per round)
   bool pool_one_pass = true;          // segment path: pool2 of all phases in one pass (same bits)
   bool pool_fused = true;             // segment path, phases {0, 2}: pool2 in conv4's epilogue (EXPECTO_POOL_FUSED; same bits)
@@ -1636,8 +1659,7 @@ struct expecto_beluga {
   float* fk_h1 = nullptr;
   long long* fk_arows = nullptr;
   long long* fk_crows = nullptr;
-  int* fk_gres = nullptr;
-  long long fk_gres_cap = 0;
+  int* fk_gres = nullptr;            //   kGresPerBatch * max_batch entries (a chunk's conv6 blocks)
   float* fk_aseq[3] = {};             //   segment pairs' in-place alt FC1: the alt blocks' sequences, row groups
   long long fk_aseq_rows = 0;
   int* fk_rgrp = nullptr;             //   of the product rows, group / window (block, row), alt windows'
@@ -2453,6 +2475,9 @@ bool fk_use_seg(const expecto_beluga* h) { return h->fk_on && h->fkw && g_precis
 // Table buffers, allocated with the first Karatsuba FC1: group starts (9 lists of <= max_batch),
 // window starts, kFkParts partial rows per window, kFkParts x tiles alt-mask words.
 int fk_cap(const expecto_beluga* h) { return std::max(h->max_batch, h->fk_slice); }
+// fk_gres entries per max_batch: a segment chunk's conv6 blocks nb keep their conv5 rows in Q,
+// nb * T5 * 640 <= max_batch * 496 * 320 with T5 >= 113 (segments of >= 2000 bases): nb < 2.2 max_batch
+constexpr int kGresPerBatch = 3;
 
 int fk_tables(expecto_beluga* h) {
   if (h->fk_grows) return EXPECTO_OK;
@@ -2469,8 +2494,8 @@ int fk_tables(expecto_beluga* h) {
   return EXPECTO_OK;
 }
 
-// Segment-path FC1 launches of up to fk_cap windows (one launch per strand for the 200-window
-// workload's 19,200 windows: one round structure instead of three part-filled ones): partial rows,
+// Segment-path FC1 launches of up to fk_cap windows (the 200-window workload's 2 x 19,200 windows
+// in launches of 24,576 + 13,824: one round structure each instead of part-filled ones): partial rows,
 // FC1 output rows, window starts and output rows, allocated with the first segment call.
 int fk_seg_buffers(expecto_beluga* h) {
   if (h->fk_part) return EXPECTO_OK;
@@ -2662,17 +2687,18 @@ int fk_fc1(expecto_beluga* h, const float* x, float* const* seq, const FkProduct
   return prow ? fk_reduce(h, part, prow, n, h1, st) : EXPECTO_OK;
 }
 
-// A window of the segment path for the Karatsuba FC1: its conv6 block (segment - s0, pool2 phase) and
+// A window of the segment path for the Karatsuba FC1 (w: its number; off: its offset in its segment,
+// chunk block `seg`, strand rc): its conv6 block (seg, pool2 phase) and
 // offset in conv6 rows (as seg_a_rows computes them); its role is its 25-row step mod 4 and its
 // group the windows of its block with the same group start off6 - 25 role.
 struct FkWin {
   int w, blk, off6;
 };
 int fk_role_of(int off6) { return (off6 / 25) & 3; }
-FkWin fk_win(int w, const int* win_seg, const int* win_off, int s0, bool rc, int L, int n_ph, const int* ph_idx) {
-  const int o = rc ? L - kLen - win_off[w] : win_off[w];
+FkWin fk_win(int w, int seg, int off, bool rc, int L, int n_ph, const int* ph_idx) {
+  const int o = rc ? L - kLen - off : off;
   const int q = o >> 2, p = q & 3;
-  return {w, (win_seg[w] - s0) * n_ph + ph_idx[p], (q - p) >> 2};
+  return {w, seg * n_ph + ph_idx[p], (q - p) >> 2};
 }
 bool fk_same_group(const FkWin& a, const FkWin& b) {
   return a.blk == b.blk && a.off6 - 25 * fk_role_of(a.off6) == b.off6 - 25 * fk_role_of(b.off6);
@@ -2912,19 +2938,30 @@ int forward_segments(expecto_beluga* h, const uint8_t* codes, int n_seg, int L, 
       *b = nullptr;
     }
     h->win_cap = 0;
-    for (int** b : {&h->win_seg_d, &h->win_off_d, &h->win_row_d, &h->alt_w_d, &h->copy_w_d})
-      EXPECTO_HIP_CHECK(hipMalloc(b, n_win * sizeof(int)));
+    for (int** b : {&h->win_seg_d, &h->win_off_d, &h->win_row_d}) EXPECTO_HIP_CHECK(hipMalloc(b, n_win * sizeof(int)));
+    for (int** b : {&h->alt_w_d, &h->copy_w_d}) EXPECTO_HIP_CHECK(hipMalloc(b, 2 * n_win * sizeof(int)));   // per strand
     EXPECTO_HIP_CHECK(hipMalloc(&h->fc_perm_d, 4 * n_win * sizeof(int)));   // per strand: FC order, alt order
     h->win_cap = n_win;
   }
-  std::vector<int> alt_w, copy_w;
+  // (strand, segment) entries and their windows, the fwd strand's first (SegStrands)
+  const int strands = mode == EXPECTO_STRAND_BOTH ? 2 : 1;
+  const int n_ent = strands * n_seg, n_vw = strands * n_win;
+  const SegStrands ss{n_seg, mode == EXPECTO_STRAND_FWD ? n_ent : mode == EXPECTO_STRAND_RC ? 0 : n_seg,
+                      n_win, mode == EXPECTO_STRAND_FWD ? n_vw : mode == EXPECTO_STRAND_RC ? 0 : n_win,
+                      pr ? pr->strand_stride : n_win};
+  auto vw_w = [&](int v) { return v >= n_win ? v - n_win : v; };
+  std::vector<int> vfirst(n_ent + 1, n_vw);   // first window of entry e
+  for (int e = 0; e < n_ent; ++e) vfirst[e] = e >= n_seg ? n_win + first[e - n_seg] : first[e];
+  std::vector<char> is_alt(n_win, 0);
+  std::vector<int> alt_w, copy_w;   // window numbers, ascending
   if (pr) {
     for (int sg = 0; sg < n_seg; ++sg)
       EXPECTO_REQUIRE(pr->var_pos[sg] >= 0 && pr->var_pos[sg] < L, "variant position outside its segment");
     for (int w = 0; w < n_win; ++w) {
       const int q = pr->var_pos[win_seg[w]];
-      (win_off[w] <= q && q < win_off[w] + kLen ? alt_w : copy_w).push_back(w);
+      is_alt[w] = win_off[w] <= q && q < win_off[w] + kLen;
     }
+    for (int v = 0; v < n_vw; ++v) (is_alt[vw_w(v)] ? alt_w : copy_w).push_back(v);
     if (n_seg > h->seg_var_cap) {
       if (h->seg_var_d) EXPECTO_HIP_CHECK(hipFree(h->seg_var_d));
       h->seg_var_d = nullptr;
@@ -2945,49 +2982,47 @@ int forward_segments(expecto_beluga* h, const uint8_t* codes, int n_seg, int L, 
   }
   copies.push_back({h->win_seg_d, win_seg, n_win * sizeof(int)});
   copies.push_back({h->win_off_d, win_off, n_win * sizeof(int)});
-  const int strands = mode == EXPECTO_STRAND_BOTH ? 2 : 1;
   // alt runs: one block per segment (conv1..4) or per (segment, phase) (pool2, conv5, conv6)
   const int blk_per_seg = pr ? std::max(n_ph, 1) : 0;
-  // chunks of whole segments: grow while the segment buffers and the alt-run buffers (<= max_batch
-  // blocks) fit.  The FC stage of a chunk runs in slices of <= max_batch windows (its workspace),
-  // so a chunk is not bounded by its window count: one large chunk instead of several keeps every
-  // conv launch's last partial round of 256 workgroups to one per chunk (the 200-window workload:
-  // 96 segments per strand in one chunk instead of 40 + 40 + 16)
+  // chunks of whole (strand, segment) entries: grow while the segment buffers and the alt-run
+  // buffers (<= max_batch blocks) fit.  The FC stage of a chunk runs in slices of <= max_batch
+  // windows (its workspace), so a chunk is not bounded by its window count: one large chunk instead
+  // of several keeps every conv launch's last partial round of 256 workgroups to one per chunk (the
+  // 200-window workload: 96 segments per strand in one chunk instead of 40 + 40 + 16), and a chunk
+  // runs on across the strand boundary (both strands' 192 entries in one chunk: every stage is
+  // launched once per step, not once per strand; EXPECTO_SEG_MERGE_STRANDS=0 ends a chunk there)
   std::vector<std::pair<int, int>> chunks;
-  for (int s0 = 0; s0 < n_seg;) {
-    int s1 = s0 + 1;
-    while (s1 < n_seg && s1 - s0 < seg_cap && (long long)(s1 + 1 - s0) * blk_per_seg <= h->max_batch &&
-           (h->seg_chunk_windows <= 0 || first[s1 + 1] - first[s0] <= h->seg_chunk_windows))
-      ++s1;
-    chunks.push_back({s0, s1});
-    s0 = s1;
+  for (int e0 = 0; e0 < n_ent;) {
+    int e1 = e0 + 1;
+    while (e1 < n_ent && (e1 != n_seg || h->seg_merge_strands) && e1 - e0 < seg_cap &&
+           (long long)(e1 + 1 - e0) * blk_per_seg <= h->max_batch &&
+           (h->seg_chunk_windows <= 0 || vfirst[e1 + 1] - vfirst[e0] <= h->seg_chunk_windows))
+      ++e1;
+    chunks.push_back({e0, e1});
+    e0 = e1;
   }
   // Segment pairs: the FC rows of a chunk are its alt windows sorted by the SNV's position in
-  // the window, then the other windows.  The ref FC1 runs in that order, and the alt FC1 over
-  // the first rows recomputes only the split-K slabs its changed conv6 rows touch (a 256-row
-  // tile then holds windows with nearly the same changed rows), reusing the ref partials.
+  // the window (in the window's strand orientation), then the other windows.  The ref FC1 runs in
+  // that order, and the alt FC1 over the first rows recomputes only the split-K slabs its changed
+  // conv6 rows touch (a 256-row tile then holds windows with nearly the same changed rows), reusing
+  // the ref partials.
   std::vector<int> fc_perm;
   if (pr) {
-    fc_perm.resize((size_t)strands * n_win);
-    std::vector<char> is_alt(n_win, 0);
-    for (int w : alt_w) is_alt[w] = 1;
-    for (int sd = 0; sd < strands; ++sd) {
-      const bool rcs = (mode == EXPECTO_STRAND_RC) || sd == 1;
-      int* out = fc_perm.data() + (size_t)sd * n_win;
-      for (const auto& c : chunks) {
-        const int w0 = first[c.first], w1 = first[c.second];
-        int k = w0;
-        std::vector<int> a;
-        for (int w = w0; w < w1; ++w)
-          if (is_alt[w]) a.push_back(w);
-        std::stable_sort(a.begin(), a.end(), [&](int x, int y) {
-          const int px = pr->var_pos[win_seg[x]] - win_off[x], py = pr->var_pos[win_seg[y]] - win_off[y];
-          return rcs ? px > py : px < py;
-        });
-        for (int w : a) out[k++] = w;
-        for (int w = w0; w < w1; ++w)
-          if (!is_alt[w]) out[k++] = w;
-      }
+    fc_perm.resize((size_t)n_vw);
+    auto pos_of = [&](int v) {
+      const int w = vw_w(v), p = pr->var_pos[win_seg[w]] - win_off[w];
+      return v >= ss.rc_win ? kLen - 1 - p : p;
+    };
+    for (const auto& c : chunks) {
+      const int w0 = vfirst[c.first], w1 = vfirst[c.second];
+      int k = w0;
+      std::vector<int> a;
+      for (int v = w0; v < w1; ++v)
+        if (is_alt[vw_w(v)]) a.push_back(v);
+      std::stable_sort(a.begin(), a.end(), [&](int x, int y) { return pos_of(x) < pos_of(y); });
+      for (int v : a) fc_perm[k++] = v;
+      for (int v = w0; v < w1; ++v)
+        if (!is_alt[vw_w(v)]) fc_perm[k++] = v;
     }
     copies.push_back({h->fc_perm_d, fc_perm.data(), fc_perm.size() * sizeof(int)});
   }
@@ -2998,459 +3033,443 @@ int forward_segments(expecto_beluga* h, const uint8_t* codes, int n_seg, int L, 
   // window) run the direct FC1 (role 4): an alt window's Karatsuba products mix rows 25-75 apart, so
   // nearly all of them reach the changed rows and the alt recompute outweighs the saving
   // (configs[2]: 14.4 k vs 16.6 k variants/s); the 200-window sweeps (5 % alt windows) gain.
-  const bool fkm = fk_use_seg(h) && !(pr && 3 * alt_w.size() > (size_t)n_win);
-  std::vector<std::vector<FkWin>> fk_ref, fk_alt;   // [strand * chunks + chunk]
-  std::vector<char> fk_is_alt(pr ? n_win : 0, 0);
-  for (int w : alt_w) fk_is_alt[w] = 1;
+  const bool fkm = fk_use_seg(h) && !(pr && 3 * alt_w.size() > (size_t)n_vw);
+  std::vector<std::vector<FkWin>> fk_ref, fk_alt;   // [chunk]
+  auto fk_is_alt = [&](int v) { return is_alt[vw_w(v)] != 0; };
   if (fkm) {
     fc_perm.assign((size_t)4 * n_win, 0);
-    for (int sd = 0; sd < strands; ++sd) {
-      const bool rcs = (mode == EXPECTO_STRAND_RC) || sd == 1;
-      for (const auto& c : chunks) {
-        const int w0 = first[c.first], w1 = first[c.second];
-        // group order: (segment pairs) the groups holding an alt window first, ordered by where the
-        // SNV falls in the group (so an M tile of the in-place alt FC1 holds groups whose changed
-        // products are the same and its masks stay sparse), then every other group; in a group its
-        // windows by role
-        struct Key {
-          int cls;
-          long long rel;
-          int blk, G, off6, w;
-        };
-        std::vector<FkWin> ref, alt;
-        std::vector<Key> key;
-        std::map<std::pair<int, int>, int> galt;   // (block, group start) -> holds an alt window
-        for (int w = w0; w < w1; ++w) {
-          const FkWin fw = fk_win(w, win_seg, win_off, c.first, rcs, L, n_ph, ph_idx);
-          ref.push_back(fw);
-          if (pr && fk_is_alt[w]) {
-            alt.push_back(fw);
-            galt[{fw.blk, fw.off6 - 25 * fk_role_of(fw.off6)}] = 1;
-          }
+    for (const auto& c : chunks) {
+      const int w0 = vfirst[c.first], w1 = vfirst[c.second];
+      // group order: (segment pairs) the groups holding an alt window first, ordered by where the
+      // SNV falls in the group (so an M tile of the in-place alt FC1 holds groups whose changed
+      // products are the same and its masks stay sparse), then every other group; in a group its
+      // windows by role
+      struct Key {
+        int cls;
+        long long rel;
+        int blk, G, off6, w;
+      };
+      std::vector<FkWin> ref, alt;
+      std::vector<Key> key;
+      std::map<std::pair<int, int>, int> galt;   // (block, group start) -> holds an alt window
+      for (int v = w0; v < w1; ++v) {   // a group lies in one block, so it never mixes strands
+        const int w = vw_w(v);
+        const FkWin fw = fk_win(v, win_seg[w] + (v >= n_win ? n_seg : 0) - c.first, win_off[w], v >= ss.rc_win, L, n_ph,
+                                ph_idx);
+        ref.push_back(fw);
+        if (pr && fk_is_alt(v)) {
+          alt.push_back(fw);
+          galt[{fw.blk, fw.off6 - 25 * fk_role_of(fw.off6)}] = 1;
         }
-        for (const FkWin& fw : ref) {
-          const int G = fw.off6 - 25 * fk_role_of(fw.off6);
-          const bool ga = pr && galt.count({fw.blk, G});
-          long long rel = 0;
-          if (ga) {
-            const int q = pr->var_pos[win_seg[fw.w]];
-            rel = (long long)(rcs ? L - 1 - q : q) - 16LL * G;
-          }
-          key.push_back({ga ? 0 : 1, rel, fw.blk, G, fw.off6, fw.w});
-        }
-        std::vector<int> ord(ref.size());
-        for (size_t k = 0; k < ord.size(); ++k) ord[k] = (int)k;
-        std::sort(ord.begin(), ord.end(), [&](int a, int b) {
-          const Key &x = key[a], &y = key[b];
-          return std::tie(x.cls, x.rel, x.blk, x.G, x.off6, x.w) < std::tie(y.cls, y.rel, y.blk, y.G, y.off6, y.w);
-        });
-        std::vector<FkWin> sorted;
-        for (int k : ord) sorted.push_back(ref[k]);
-        for (size_t k = 0; k < sorted.size(); ++k) fc_perm[(size_t)sd * n_win + w0 + k] = sorted[k].w;
-        fk_ref.push_back(std::move(sorted));
-        fk_alt.push_back(std::move(alt));
       }
+      for (const FkWin& fw : ref) {
+        const int G = fw.off6 - 25 * fk_role_of(fw.off6);
+        const bool ga = pr && galt.count({fw.blk, G});
+        long long rel = 0;
+        if (ga) {
+          const int q = pr->var_pos[win_seg[vw_w(fw.w)]];
+          rel = (long long)(fw.w >= ss.rc_win ? L - 1 - q : q) - 16LL * G;
+        }
+        key.push_back({ga ? 0 : 1, rel, fw.blk, G, fw.off6, fw.w});
+      }
+      std::vector<int> ord(ref.size());
+      for (size_t k = 0; k < ord.size(); ++k) ord[k] = (int)k;
+      std::sort(ord.begin(), ord.end(), [&](int a, int b) {
+        const Key &x = key[a], &y = key[b];
+        return std::tie(x.cls, x.rel, x.blk, x.G, x.off6, x.w) < std::tie(y.cls, y.rel, y.blk, y.G, y.off6, y.w);
+      });
+      std::vector<FkWin> sorted;
+      for (int k : ord) sorted.push_back(ref[k]);
+      for (size_t k = 0; k < sorted.size(); ++k) fc_perm[(size_t)w0 + k] = sorted[k].w;
+      fk_ref.push_back(std::move(sorted));
+      fk_alt.push_back(std::move(alt));
     }
     if (pr) copies.pop_back();   // the pair order above is replaced by the group order
     copies.push_back({h->fc_perm_d, fc_perm.data(), fc_perm.size() * sizeof(int)});
   }
   // the tables are caller-owned (and local) host memory: stage them through pinned memory
   if ((rc = stage_copies(h, copies, st))) return rc;
-  const long long strand_rows = pr ? pr->strand_stride : n_win;
   const int eb = act_bytes();
   hipStream_t sa = (pr && h->st2) ? h->st2 : st;     // alt runs of segment pairs
   const SegDims gd{L, g.T1, g.P1, g.T3, g.T4, g.S5, g.T5, g.T6};
   const int4 ph4 = make_int4(ph[0], ph[1], ph[2], ph[3]);
-  for (int sd = 0; sd < strands; ++sd) {
-    const bool is_rc = (mode == EXPECTO_STRAND_RC) || sd == 1;
-    for (const auto& chunk : chunks) {
-      const int s0 = chunk.first, s1 = chunk.second;
-      const int w0 = first[s0], nw = first[s1] - first[s0];
-      const int ns = s1 - s0;
-      const long long nb = (long long)ns * n_ph;
-      // Alt runs (segment pairs) on the handle's second stream `sa`: the alt input patch of
-      // layer l is assembled from the ref input of layer l (`ref`, ref_rows per block; the
-      // ref layer l reads it concurrently) and the previous alt run, then the layer's GEMM runs
-      // on it beside the next ref layers.  The ref launch that next overwrites `ref` (ping-
-      // pong) waits for the assembly (event `done`).  Same kernels, K order and weights.
-      auto alt_asm = [&](int l, const float* ref, int ref_rows, const float* dprev, int wprev, int nbk, int ib,
-                         int mult, int irp, int arows, hipEvent_t ready, hipEvent_t done) -> int {
-        if (sa != st) {
-          EXPECTO_HIP_CHECK(hipEventRecord(ready, st));
-          EXPECTO_HIP_CHECK(hipStreamWaitEvent(sa, ready, 0));
-        }
-        const int row16 = kConv[l].cin * eb / 16;
-        seg_delta_assemble<<<dim3(ns * nbk), dim3(256), 0, sa>>>(ref, ref_rows, dprev, wprev, h->seg_tab, nbk,
-                                                                      ib, mult, irp, arows, row16, h->DA);
-        int r = check_launch("seg_delta_assemble");
-        if (!r && sa != st) EXPECTO_HIP_CHECK(hipEventRecord(done, sa));
-        return r;
-      };
-      auto alt_gemm = [&](int l, int nbk, int arows, int w, bool pool, float* dnext) -> int {
+  for (const auto& chunk : chunks) {
+    const int s0 = chunk.first, s1 = chunk.second;   // entries [s0, s1), windows [w0, w0 + nw)
+    const int w0 = vfirst[s0], nw = vfirst[s1] - vfirst[s0];
+    const int ns = s1 - s0;
+    const long long nb = (long long)ns * n_ph;
+    // Alt runs (segment pairs) on the handle's second stream `sa`: the alt input patch of
+    // layer l is assembled from the ref input of layer l (`ref`, ref_rows per block; the
+    // ref layer l reads it concurrently) and the previous alt run, then the layer's GEMM runs
+    // on it beside the next ref layers.  The ref launch that next overwrites `ref` (ping-
+    // pong) waits for the assembly (event `done`).  Same kernels, K order and weights.
+    auto alt_asm = [&](int l, const float* ref, int ref_rows, const float* dprev, int wprev, int nbk, int ib,
+                       int mult, int irp, int arows, hipEvent_t ready, hipEvent_t done) -> int {
+      if (sa != st) {
+        EXPECTO_HIP_CHECK(hipEventRecord(ready, st));
+        EXPECTO_HIP_CHECK(hipStreamWaitEvent(sa, ready, 0));
+      }
+      const int row16 = kConv[l].cin * eb / 16;
+      seg_delta_assemble<<<dim3(ns * nbk), dim3(256), 0, sa>>>(ref, ref_rows, dprev, wprev, h->seg_tab, nbk,
+                                                                    ib, mult, irp, arows, row16, h->DA);
+      int r = check_launch("seg_delta_assemble");
+      if (!r && sa != st) EXPECTO_HIP_CHECK(hipEventRecord(done, sa));
+      return r;
+    };
+    auto alt_gemm = [&](int l, int nbk, int arows, int w, bool pool, float* dnext) -> int {
+      DeltaScope ds(h);
+      return run_conv(h, l, h->DA, dnext, (long long)ns * nbk, arows, w, w, pool, sa);
+    };
+    auto st_wait = [&](hipEvent_t e) -> int {   // st: the alt work recorded in e is done
+      if (sa != st) EXPECTO_HIP_CHECK(hipStreamWaitEvent(st, e, 0));
+      return EXPECTO_OK;
+    };
+    if (pr && sa != st) {   // sa: the previous chunk's use of the alt buffers on st is done
+      EXPECTO_HIP_CHECK(hipEventRecord(h->pev[0], st));
+      EXPECTO_HIP_CHECK(hipStreamWaitEvent(sa, h->pev[0], 0));
+    }
+    // conv1 from codes: virtual rows = the chunk's entries, code rows s0.. of the call's n_seg in
+    // its strand mode (BOTH: rows >= n_seg are the rc strand's); the kernel mirrors the rc rows
+    // (fused: inside the conv2 launch)
+    const bool kmer = use_kmer(h, nullptr);
+    const bool fuse = !kmer && fuse_conv1(h, nullptr);
+    const C1Src f1{codes, code_stride, n_seg, mode, s0, L};
+    if (!kmer && !fuse && (rc = run_conv1(h, nullptr, codes, code_stride, n_seg, mode, s0, ns, L, g.S1, st)))
+      return rc;
+    if (pr) {
+      seg_delta_table<<<dim3((ns + 255) / 256), dim3(256), 0, sa>>>(h->seg_var_d, s0, ns, ss, gd, n_ph, ph4,
+                                                                   h->seg_tab);
+      if ((rc = check_launch("seg_delta_table"))) return rc;
+      if (kmer || fuse) {   // the alt conv2 patch straight from the alt codes (k-mer table, or conv1 -> DA)
+        seg_delta_codes2<<<dim3((ns + 4) / 5), dim3(5 * kC1PatStride), 0, sa>>>(
+            codes, code_stride, pr->alt_code, s0, ns, ss, L, h->seg_tab, h->delta_codes);
+        if ((rc = check_launch("seg_delta_codes2"))) return rc;
         DeltaScope ds(h);
-        return run_conv(h, l, h->DA, dnext, (long long)ns * nbk, arows, w, w, pool, sa);
-      };
-      auto st_wait = [&](hipEvent_t e) -> int {   // st: the alt work recorded in e is done
-        if (sa != st) EXPECTO_HIP_CHECK(hipStreamWaitEvent(st, e, 0));
-        return EXPECTO_OK;
-      };
-      if (pr && sa != st) {   // sa: the previous chunk's use of the alt buffers on st is done
-        EXPECTO_HIP_CHECK(hipEventRecord(h->pev[0], st));
-        EXPECTO_HIP_CHECK(hipStreamWaitEvent(sa, h->pev[0], 0));
-      }
-      // conv1 from codes: virtual rows = segments; rc mode mirrors inside the kernel (fused: inside
-      // the conv2 launch)
-      const bool kmer = use_kmer(h, nullptr);
-      const bool fuse = !kmer && fuse_conv1(h, nullptr);
-      const C1Src f1{codes + (long long)s0 * code_stride, code_stride, ns, is_rc ? EXPECTO_STRAND_RC : EXPECTO_STRAND_FWD,
-                     0, L};
-      if (!kmer && !fuse && (rc = run_conv1(h, nullptr, f1.codes, code_stride, ns, f1.mode, 0, ns, L, g.S1, st)))
-        return rc;
-      if (pr) {
-        seg_delta_table<<<dim3((ns + 255) / 256), dim3(256), 0, sa>>>(h->seg_var_d, s0, ns, is_rc ? 1 : 0, gd, n_ph,
-                                                                     ph4, h->seg_tab);
-        if ((rc = check_launch("seg_delta_table"))) return rc;
-        if (kmer || fuse) {   // the alt conv2 patch straight from the alt codes (k-mer table, or conv1 -> DA)
-          seg_delta_codes2<<<dim3((ns + 4) / 5), dim3(5 * kC1PatStride), 0, sa>>>(
-              codes, code_stride, pr->alt_code, s0, ns, is_rc ? 1 : 0, L, h->seg_tab, h->delta_codes);
-          if ((rc = check_launch("seg_delta_codes2"))) return rc;
-          DeltaScope ds(h);
-          if (fuse && (rc = run_conv1(h, nullptr, h->delta_codes, kC1PatStride, ns, EXPECTO_STRAND_FWD, 0, ns, kC1Pat,
-                                      kDA[2], sa, h->DA)))
-            return rc;
-        } else {
-          seg_delta_codes<<<dim3((ns + 15) / 16), dim3(256), 0, sa>>>(codes, code_stride, pr->alt_code, s0, ns,
-                                                                     is_rc ? 1 : 0, L, h->seg_tab, h->delta_codes);
-          if ((rc = check_launch("seg_delta_codes"))) return rc;
-          DeltaScope ds(h);
-          if ((rc = run_conv1(h, nullptr, h->delta_codes, 16, ns, EXPECTO_STRAND_FWD, 0, ns, kDA[1], kDW[1], sa,
-                              h->D0)))
-            return rc;
-        }
-      }
-      // conv2 + pool1 (P -> Q), conv3 (Q -> P), conv4 unpooled (P -> Q); alt runs D0 <-> D1
-      if (pr && !kmer && !fuse && (rc = alt_asm(0, h->P, g.S1, h->D0, kDW[1], 1, 2, 4, 1, kDA[2], h->pev[1], h->pev[2])))
-        return rc;
-      if (kmer)
-        rc = run_conv2_kmer(h, f1, ns, g.P1, g.P1, h->Q, st);
-      else
-        rc = run_conv(h, 0, h->P, h->Q, ns, g.S1, g.P1, g.P1, true, st, fuse ? &f1 : nullptr);
-      if (rc) return rc;
-      if (pr && kmer) {   // alt pooled conv2 rows [r2, r2 + kDW[2]) of each segment into D1
-        DeltaScope ds(h);
-        const C1Src fa{h->delta_codes, kC1PatStride, ns, EXPECTO_STRAND_FWD, 0, kC1Pat};
-        if ((rc = run_conv2_kmer(h, fa, ns, kDW[2], kDW[2], h->D1, sa))) return rc;
-      } else if (pr && ((!fuse && (rc = st_wait(h->pev[2]))) || (rc = alt_gemm(0, 1, kDA[2], kDW[2], true, h->D1)))) {
-        return rc;
-      }
-      if (pr && (rc = alt_asm(1, h->Q, g.P1, h->D1, kDW[2], 1, 3, 1, 2, kDA[3], h->pev[3], h->pev[4]))) return rc;
-      // conv3 rows at a 4-aligned stride per segment (T3p >= T3), so conv4's rows of every segment
-      // start 4-aligned in its M index space: pool2 groups are then lane-local (epilogue_pool_ph02)
-      const int T3p = (g.T3 + 3) & ~3;
-      if ((rc = run_conv(h, 1, h->Q, h->P, ns, g.P1, g.T3, T3p, false, st))) return rc;
-      if (pr && ((rc = st_wait(h->pev[4])) || (rc = alt_gemm(1, 1, kDA[3], kDW[3], false, h->D0)))) return rc;
-      if (pr && (rc = alt_asm(2, h->P, T3p, h->D0, kDW[3], 1, 4, 1, 3, kA4u, h->pev[5], h->pev[6]))) return rc;
-      // pool2 fused into conv4 (P -> phase blocks in Q, then P and Q trade roles for the rest of
-      // the chunk: conv5 Q -> P, conv6 P -> Q, ... -- both hold a chunk's conv5 / conv6 rows, see
-      // seg_geo), else conv4 unpooled (P -> Q) and a pool pass (Q -> P)
-      const bool pfused = conv4_pool_fused(h, (long long)ns * T3p, n_ph, ph);
-      struct PQSwap {
-        expecto_beluga* h;
-        bool on;
-        ~PQSwap() {
-          if (on) std::swap(h->P, h->Q);
-        }
-      } pq{h, false};
-      if (pfused) {
-        if ((rc = run_conv4_pool_fused(h, h->P, h->Q, ns, T3p, g.T4, g.S5, pr ? h->seg_tab : nullptr, st))) return rc;
-        std::swap(h->P, h->Q);
-        pq.on = true;
-      } else if ((rc = run_conv(h, 2, h->P, h->Q, ns, T3p, g.T4, g.T4, false, st))) {
-        return rc;
-      }
-      if (pr && ((rc = st_wait(h->pev[6])) || (rc = alt_gemm(2, 1, kA4u, kW4u, false, h->D1)))) return rc;
-      if (!pfused) {  // pool2 phases (Q -> P)
-        LayerTimer lt(h, 3, st);
-        if (act_fmt() == 2 && h->pool_one_pass) {   // all phases in one pass over the conv4 rows
-          dim3 grid((g.S5 + 3) / 4, ns);
-          pool4_phases_h2m<<<grid, dim3(256), 0, st>>>(h->Q, g.T4, g.T4, 480, n_ph, ph4, g.S5, h->P);
-        } else if (act_fmt() == 2) {
-          dim3 grid((g.S5 + 3) / 4, ns * n_ph);
-          pool4_phases_h2<<<grid, dim3(256), 0, st>>>(h->Q, g.T4, g.T4, 480, n_ph, ph4, g.S5, h->P);
-        } else {
-          dim3 grid(g.S5, ns * n_ph);
-          pool4_phases<<<grid, dim3(480), 0, st>>>(h->Q, ns, g.T4, g.T4, 480, n_ph, ph4, g.S5, h->P, act_fmt());
-        }
-        if ((rc = check_launch("pool4_phases"))) return rc;
-      }
-      if (pr) {   // alt pool2 phases from the unpooled conv4 rows (Q) and the alt conv4 run
-        if (sa != st) {
-          EXPECTO_HIP_CHECK(hipEventRecord(h->pev[7], st));
-          EXPECTO_HIP_CHECK(hipStreamWaitEvent(sa, h->pev[7], 0));
-        }
-        seg_delta_pool<<<dim3(kDW[4], (unsigned)nb), dim3(480), 0, sa>>>(pfused ? h->edge : h->Q, g.T4, h->D1, n_ph,
-                                                                         ph4, h->seg_tab, act_fmt(), h->D0,
-                                                                         pfused ? 1 : 0);
-        if ((rc = check_launch("seg_delta_pool"))) return rc;
-        if (sa != st) EXPECTO_HIP_CHECK(hipEventRecord(h->pev[8], sa));
-        if ((rc = alt_asm(3, h->P, g.S5, h->D0, kDW[4], n_ph, 9, 1, 5, kDA[5], h->pev[9], h->pev[10]))) return rc;
-        if ((rc = st_wait(h->pev[8]))) return rc;    // conv5 overwrites Q
-      }
-      // conv5 (P -> Q), conv6 (Q -> P) over (segment, phase) blocks
-      if ((rc = run_conv(h, 3, h->P, h->Q, nb, g.S5, g.T5, g.T5, false, st))) return rc;
-      if (pr && ((rc = st_wait(h->pev[10])) || (rc = alt_gemm(3, n_ph, kDA[5], kDW[5], false, h->D1)))) return rc;
-      if (pr && (rc = alt_asm(4, h->Q, g.T5, h->D1, kDW[5], n_ph, 13, 1, 9, kDA[6], h->pev[11], h->pev[12])))
-        return rc;
-      if ((rc = run_conv(h, 4, h->Q, h->P, nb, g.T5, g.T6, g.T6, false, st))) return rc;
-      if (pr) {
-        if ((rc = alt_gemm(4, n_ph, kDA[6], kDW[6], false, h->D0))) return rc;
-        if (sa != st) EXPECTO_HIP_CHECK(hipEventRecord(h->pev[13], sa));   // all alt runs of the chunk
-      }
-      if (nw > 0 && fkm) {
-        // FC1 as the block Karatsuba: the conv6 blocks' D1 / D2 / DD, then slices of whole window
-        // groups (<= fk_cap windows) in group order: window starts and output rows (seg_a_rows),
-        // the slice's product and partial-row tables (host, staged), one grouped FC1 launch, FC2.
-        // Segment pairs: the groups holding alt windows come first in the first slice; right after
-        // it, the alt FC1 runs IN PLACE over that slice's partial rows -- the alt blocks' sequences
-        // (Q), only the (product, slab, tail) partials the SNV's changed conv6 rows reach (masks per
-        // M tile), the ref partials for the rest -- and the alt windows' rows are reduced and FC2'd.
-        const int4 phi = make_int4(ph_idx[0], ph_idx[1], ph_idx[2], ph_idx[3]);
-        const long long row_base = (long long)sd * strand_rows;
-        const size_t ci = (size_t)sd * chunks.size() + (size_t)(&chunk - chunks.data());
-        const long long cap = fk_cap(h);
-        const std::vector<FkWin>& ws = fk_ref[ci];
-        const int* perm = h->fc_perm_d + (size_t)sd * n_win + w0;
-        // per conv6 block: its groups' start residue mod 100 (all equal on 200-bp sweeps), so the
-        // sequences are formed only on the rows the products read; -2: a block no window reads
-        std::vector<int> gres((size_t)nb, -2);
-        for (const FkWin& w : ws) {
-          const int r = (w.off6 - 25 * fk_role_of(w.off6)) % 100;
-          int& e = gres[(size_t)w.blk];
-          e = e == -2 ? r : (e == r ? r : -1);
-        }
-        if (nb > h->fk_gres_cap) {
-          if (h->fk_gres) EXPECTO_HIP_CHECK(hipFree(h->fk_gres));
-          h->fk_gres = nullptr;
-          h->bytes -= (size_t)h->fk_gres_cap * sizeof(int);
-          h->fk_gres_cap = 0;
-          EXPECTO_HIP_CHECK(hipMalloc(&h->fk_gres, (size_t)nb * sizeof(int)));
-          h->fk_gres_cap = nb;
-          h->bytes += (size_t)nb * sizeof(int);
-        }
-        if ((rc = stage_copies(h, {{h->fk_gres, gres.data(), gres.size() * sizeof(int)}}, st)) || (rc = fk_tables(h)) ||
-            (rc = fk_seg_buffers(h)) || (rc = fk_sequences(h, h->P, nb, g.T6, g.T6, nullptr, n_ph, st, h->fk_gres)))
+        if (fuse && (rc = run_conv1(h, nullptr, h->delta_codes, kC1PatStride, ns, EXPECTO_STRAND_FWD, 0, ns, kC1Pat,
+                                    kDA[2], sa, h->DA)))
           return rc;
-        const bool has_alt = pr && !fk_alt[ci].empty();
-        bool alt_ready = false;   // alt conv6 blocks (Q) and their sequences formed (once per chunk)
-        for (size_t i0 = 0; i0 < ws.size();) {
-          size_t i1 = i0;
-          while (i1 < ws.size()) {   // whole groups, <= fk_cap windows
-            size_t j = i1 + 1;
-            while (j < ws.size() && fk_same_group(ws[j], ws[i1])) ++j;
-            if (j - i0 > (size_t)cap && i1 > i0) break;
-            i1 = j;
-          }
-          EXPECTO_REQUIRE(i1 - i0 <= (size_t)cap, "a Karatsuba FC1 window group exceeds the FC1 slice");
-          const int fn = (int)(i1 - i0);
-          std::vector<long long> grows;
-          std::vector<int> prow, rgrp, ginfo;
-          FkProducts prd{h->fk_grows, {}, {}, {}};
-          fk_slice_tables(ws, (int)i0, (int)i1, g.T6, grows, prd, prow, &rgrp, &ginfo);
-          if ((rc = stage_copies(h, {{h->fk_grows, grows.data(), grows.size() * sizeof(long long)},
-                                     {h->fk_prow, prow.data(), prow.size() * sizeof(int)}}, st)))
-            return rc;
-          seg_a_rows<<<dim3((fn + 255) / 256), dim3(256), 0, st>>>(
-              h->win_seg_d, h->win_off_d, win_row ? h->win_row_d : nullptr, perm + i0, 0, fn, s0, is_rc ? 1 : 0, L,
-              n_ph, phi, g.T6, row_base, h->fk_arows, h->fk_crows);
-          if ((rc = check_launch("seg_a_rows")) ||
-              (rc = fk_fc1(h, h->P, h->fk_seq, prd, h->fk_arows, fn, h->fk_prow, h->fk_h1, st, nullptr, 0, h->fk_part,
-                           kFkParts * cap)))
-            return rc;
-          for (int r0 = 0; r0 < fn; r0 += h->max_batch)   // FC2 over its workspace's max_batch rows at a time
-            if ((rc = run_fc2(h, h->fk_h1 + (long long)r0 * kHidLd, std::min(h->max_batch, fn - r0), y, st,
-                              h->fk_crows + r0)))
-              return rc;
-          // the slice's first groups holding alt windows (the alt groups lead the chunk's order, so
-          // they fill the first slices) and their windows
-          int n_ag = 0;
-          size_t nw_pre = 0;
-          for (size_t i = i0; has_alt && i < i1; ++i) {
-            bool galt = false;
-            size_t j = i;
-            for (; j < i1 && fk_same_group(ws[j], ws[i]); ++j) galt |= fk_is_alt[ws[j].w] != 0;
-            if (!galt) break;
-            ++n_ag;
-            nw_pre = j - i0;
-            i = j - 1;
-          }
-          if (n_ag > 0) {
-            FkProducts pa = prd;   // the alt groups' prefix of every product list, in the ref layout
-            FkMaskDesc md{};
-            for (int gq = 0; gq < 9; ++gq) {
-              int c = 0;
-              for (int i = 0; i < prd.cnt[gq]; ++i)
-                if (rgrp[prd.off[gq] + i] < n_ag) ++c;
-              pa.cnt[gq] = c;
-              pa.lay[gq] = prd.cnt[gq];
-              for (int sb = 0; prd.cnt[gq] > 0 && sb < kFkSlabs; ++sb) {
-                md.g[md.n] = gq;
-                md.s[md.n] = sb;
-                md.off[md.n] = prd.off[gq];
-                md.cnt[md.n] = c;
-                ++md.n;
-              }
-            }
-            md.nw = (int)nw_pre;
-            std::vector<int> winfo, aperm, aprow;
-            for (size_t i = 0; i < nw_pre; ++i) {
-              winfo.push_back(ws[i0 + i].blk);
-              winfo.push_back(ws[i0 + i].off6);
-              if (fk_is_alt[ws[i0 + i].w]) {
-                aperm.push_back(ws[i0 + i].w);
-                aprow.insert(aprow.end(), prow.begin() + (long long)i * kFkParts, prow.begin() + (long long)(i + 1) * kFkParts);
-              }
-            }
-            const int na = (int)aperm.size();
-            const int tiles = (int)(cap / 256 + 1);
-            if ((rc = stage_copies(h, {{h->fk_rgrp, rgrp.data(), rgrp.size() * sizeof(int)},
-                                       {h->fk_ginfo, ginfo.data(), ginfo.size() * sizeof(int)},
-                                       {h->fk_winfo, winfo.data(), winfo.size() * sizeof(int)},
-                                       {h->fk_aperm, aperm.data(), aperm.size() * sizeof(int)},
-                                       {h->fk_aprow, aprow.data(), aprow.size() * sizeof(int)}}, st)))
-              return rc;
-            if (!alt_ready) {
-              if ((rc = st_wait(h->pev[13]))) return rc;   // alt conv6 runs (and the Q reads of their patches)
-              seg_alt_blocks<<<dim3(kAltRows6, (unsigned)nb), dim3(64), 0, st>>>(h->P, h->D0, n_ph, g.T6, h->seg_tab,
-                                                                                640 * eb / 16, h->Q);
-              if ((rc = check_launch("seg_alt_blocks"))) return rc;
-              DeltaScope ds(h);
-              if ((rc = fk_sequences(h, h->Q, nb, g.T6, g.T6, h->seg_tab, n_ph, st, h->fk_gres, 1))) return rc;
-              alt_ready = true;
-            }
-            EXPECTO_HIP_CHECK(hipMemsetAsync(h->fk_smask, 0, (size_t)(md.n + 1) * tiles * sizeof(unsigned), st));
-            int rows_max = md.nw;
-            for (int i = 0; i < md.n; ++i) rows_max = std::max(rows_max, md.cnt[i]);
-            if (rows_max > 0) {
-              fk_seg_mask<<<dim3((rows_max + 255) / 256, md.n + 1), dim3(256), 0, st>>>(
-                  md, h->fk_rgrp, h->fk_ginfo, h->fk_winfo, h->seg_tab, n_ph, make_int4(0, 0, 0, 0), tiles, h->fk_smask);
-              if ((rc = check_launch("fk_seg_mask"))) return rc;
-            }
-            DeltaScope ds(h);
-            if ((rc = fk_fc1(h, h->Q, h->fk_aseq, pa, h->fk_arows, (int)nw_pre, nullptr, h->fk_h1, st, h->fk_smask, tiles,
-                             h->fk_part, kFkParts * cap)) ||
-                (na > 0 && (rc = fk_reduce(h, h->fk_part, h->fk_aprow, na, h->fk_h1, st))))
-              return rc;
-            if (na > 0) {
-              seg_a_rows<<<dim3((na + 255) / 256), dim3(256), 0, st>>>(
-                  h->win_seg_d, h->win_off_d, win_row ? h->win_row_d : nullptr, h->fk_aperm, 0, na, s0, is_rc ? 1 : 0,
-                  L, n_ph, phi, g.T6, row_base, h->fk_arows, h->fk_crows);
-              if ((rc = check_launch("seg_a_rows"))) return rc;
-              for (int r0 = 0; r0 < na; r0 += h->max_batch)
-                if ((rc = run_fc2(h, h->fk_h1 + (long long)r0 * kHidLd, std::min(h->max_batch, na - r0), pr->y_alt, st,
-                                  h->fk_crows + r0)))
-                  return rc;
-            }
-          }
-          i0 = i1;
+      } else {
+        seg_delta_codes<<<dim3((ns + 15) / 16), dim3(256), 0, sa>>>(codes, code_stride, pr->alt_code, s0, ns, ss,
+                                                                   L, h->seg_tab, h->delta_codes);
+        if ((rc = check_launch("seg_delta_codes"))) return rc;
+        DeltaScope ds(h);
+        if ((rc = run_conv1(h, nullptr, h->delta_codes, 16, ns, EXPECTO_STRAND_FWD, 0, ns, kDA[1], kDW[1], sa,
+                            h->D0)))
+          return rc;
+      }
+    }
+    // conv2 + pool1 (P -> Q), conv3 (Q -> P), conv4 unpooled (P -> Q); alt runs D0 <-> D1
+    if (pr && !kmer && !fuse && (rc = alt_asm(0, h->P, g.S1, h->D0, kDW[1], 1, 2, 4, 1, kDA[2], h->pev[1], h->pev[2])))
+      return rc;
+    if (kmer)
+      rc = run_conv2_kmer(h, f1, ns, g.P1, g.P1, h->Q, st);
+    else
+      rc = run_conv(h, 0, h->P, h->Q, ns, g.S1, g.P1, g.P1, true, st, fuse ? &f1 : nullptr);
+    if (rc) return rc;
+    if (pr && kmer) {   // alt pooled conv2 rows [r2, r2 + kDW[2]) of each segment into D1
+      DeltaScope ds(h);
+      const C1Src fa{h->delta_codes, kC1PatStride, ns, EXPECTO_STRAND_FWD, 0, kC1Pat};
+      if ((rc = run_conv2_kmer(h, fa, ns, kDW[2], kDW[2], h->D1, sa))) return rc;
+    } else if (pr && ((!fuse && (rc = st_wait(h->pev[2]))) || (rc = alt_gemm(0, 1, kDA[2], kDW[2], true, h->D1)))) {
+      return rc;
+    }
+    if (pr && (rc = alt_asm(1, h->Q, g.P1, h->D1, kDW[2], 1, 3, 1, 2, kDA[3], h->pev[3], h->pev[4]))) return rc;
+    // conv3 rows at a 4-aligned stride per segment (T3p >= T3), so conv4's rows of every segment
+    // start 4-aligned in its M index space: pool2 groups are then lane-local (epilogue_pool_ph02)
+    const int T3p = (g.T3 + 3) & ~3;
+    if ((rc = run_conv(h, 1, h->Q, h->P, ns, g.P1, g.T3, T3p, false, st))) return rc;
+    if (pr && ((rc = st_wait(h->pev[4])) || (rc = alt_gemm(1, 1, kDA[3], kDW[3], false, h->D0)))) return rc;
+    if (pr && (rc = alt_asm(2, h->P, T3p, h->D0, kDW[3], 1, 4, 1, 3, kA4u, h->pev[5], h->pev[6]))) return rc;
+    // pool2 fused into conv4 (P -> phase blocks in Q, then P and Q trade roles for the rest of
+    // the chunk: conv5 Q -> P, conv6 P -> Q, ... -- both hold a chunk's conv5 / conv6 rows, see
+    // seg_geo), else conv4 unpooled (P -> Q) and a pool pass (Q -> P)
+    const bool pfused = conv4_pool_fused(h, (long long)ns * T3p, n_ph, ph);
+    struct PQSwap {
+      expecto_beluga* h;
+      bool on;
+      ~PQSwap() {
+        if (on) std::swap(h->P, h->Q);
+      }
+    } pq{h, false};
+    if (pfused) {
+      if ((rc = run_conv4_pool_fused(h, h->P, h->Q, ns, T3p, g.T4, g.S5, pr ? h->seg_tab : nullptr, st))) return rc;
+      std::swap(h->P, h->Q);
+      pq.on = true;
+    } else if ((rc = run_conv(h, 2, h->P, h->Q, ns, T3p, g.T4, g.T4, false, st))) {
+      return rc;
+    }
+    if (pr && ((rc = st_wait(h->pev[6])) || (rc = alt_gemm(2, 1, kA4u, kW4u, false, h->D1)))) return rc;
+    if (!pfused) {  // pool2 phases (Q -> P)
+      LayerTimer lt(h, 3, st);
+      if (act_fmt() == 2 && h->pool_one_pass) {   // all phases in one pass over the conv4 rows
+        dim3 grid((g.S5 + 3) / 4, ns);
+        pool4_phases_h2m<<<grid, dim3(256), 0, st>>>(h->Q, g.T4, g.T4, 480, n_ph, ph4, g.S5, h->P);
+      } else if (act_fmt() == 2) {
+        dim3 grid((g.S5 + 3) / 4, ns * n_ph);
+        pool4_phases_h2<<<grid, dim3(256), 0, st>>>(h->Q, g.T4, g.T4, 480, n_ph, ph4, g.S5, h->P);
+      } else {
+        dim3 grid(g.S5, ns * n_ph);
+        pool4_phases<<<grid, dim3(480), 0, st>>>(h->Q, ns, g.T4, g.T4, 480, n_ph, ph4, g.S5, h->P, act_fmt());
+      }
+      if ((rc = check_launch("pool4_phases"))) return rc;
+    }
+    if (pr) {   // alt pool2 phases from the unpooled conv4 rows (Q) and the alt conv4 run
+      if (sa != st) {
+        EXPECTO_HIP_CHECK(hipEventRecord(h->pev[7], st));
+        EXPECTO_HIP_CHECK(hipStreamWaitEvent(sa, h->pev[7], 0));
+      }
+      seg_delta_pool<<<dim3(kDW[4], (unsigned)nb), dim3(480), 0, sa>>>(pfused ? h->edge : h->Q, g.T4, h->D1, n_ph,
+                                                                       ph4, h->seg_tab, act_fmt(), h->D0,
+                                                                       pfused ? 1 : 0);
+      if ((rc = check_launch("seg_delta_pool"))) return rc;
+      if (sa != st) EXPECTO_HIP_CHECK(hipEventRecord(h->pev[8], sa));
+      if ((rc = alt_asm(3, h->P, g.S5, h->D0, kDW[4], n_ph, 9, 1, 5, kDA[5], h->pev[9], h->pev[10]))) return rc;
+      if ((rc = st_wait(h->pev[8]))) return rc;    // conv5 overwrites Q
+    }
+    // conv5 (P -> Q), conv6 (Q -> P) over (segment, phase) blocks
+    if ((rc = run_conv(h, 3, h->P, h->Q, nb, g.S5, g.T5, g.T5, false, st))) return rc;
+    if (pr && ((rc = st_wait(h->pev[10])) || (rc = alt_gemm(3, n_ph, kDA[5], kDW[5], false, h->D1)))) return rc;
+    if (pr && (rc = alt_asm(4, h->Q, g.T5, h->D1, kDW[5], n_ph, 13, 1, 9, kDA[6], h->pev[11], h->pev[12])))
+      return rc;
+    if ((rc = run_conv(h, 4, h->Q, h->P, nb, g.T5, g.T6, g.T6, false, st))) return rc;
+    if (pr) {
+      if ((rc = alt_gemm(4, n_ph, kDA[6], kDW[6], false, h->D0))) return rc;
+      if (sa != st) EXPECTO_HIP_CHECK(hipEventRecord(h->pev[13], sa));   // all alt runs of the chunk
+    }
+    if (nw > 0 && fkm) {
+      // FC1 as the block Karatsuba: the conv6 blocks' D1 / D2 / DD, then slices of whole window
+      // groups (<= fk_cap windows) in group order: window starts and output rows (seg_a_rows),
+      // the slice's product and partial-row tables (host, staged), one grouped FC1 launch, FC2.
+      // Segment pairs: the groups holding alt windows come first in the first slice; right after
+      // it, the alt FC1 runs IN PLACE over that slice's partial rows -- the alt blocks' sequences
+      // (Q), only the (product, slab, tail) partials the SNV's changed conv6 rows reach (masks per
+      // M tile), the ref partials for the rest -- and the alt windows' rows are reduced and FC2'd.
+      const int4 phi = make_int4(ph_idx[0], ph_idx[1], ph_idx[2], ph_idx[3]);
+      const size_t ci = (size_t)(&chunk - chunks.data());
+      const long long cap = fk_cap(h);
+      const std::vector<FkWin>& ws = fk_ref[ci];
+      const int* perm = h->fc_perm_d + w0;
+      // per conv6 block: its groups' start residue mod 100 (all equal on 200-bp sweeps), so the
+      // sequences are formed only on the rows the products read; -2: a block no window reads
+      std::vector<int> gres((size_t)nb, -2);
+      for (const FkWin& w : ws) {
+        const int r = (w.off6 - 25 * fk_role_of(w.off6)) % 100;
+        int& e = gres[(size_t)w.blk];
+        e = e == -2 ? r : (e == r ? r : -1);
+      }
+      EXPECTO_REQUIRE(nb <= kGresPerBatch * (long long)h->max_batch, "conv6 blocks of a chunk exceed fk_gres");
+      if ((rc = stage_copies(h, {{h->fk_gres, gres.data(), gres.size() * sizeof(int)}}, st)) || (rc = fk_tables(h)) ||
+          (rc = fk_seg_buffers(h)) || (rc = fk_sequences(h, h->P, nb, g.T6, g.T6, nullptr, n_ph, st, h->fk_gres)))
+        return rc;
+      const bool has_alt = pr && !fk_alt[ci].empty();
+      bool alt_ready = false;   // alt conv6 blocks (Q) and their sequences formed (once per chunk)
+      for (size_t i0 = 0; i0 < ws.size();) {
+        size_t i1 = i0;
+        while (i1 < ws.size()) {   // whole groups, <= fk_cap windows
+          size_t j = i1 + 1;
+          while (j < ws.size() && fk_same_group(ws[j], ws[i1])) ++j;
+          if (j - i0 > (size_t)cap && i1 > i0) break;
+          i1 = j;
         }
-        if (pr) {
-          const int ic0 = (int)(std::lower_bound(copy_w.begin(), copy_w.end(), w0) - copy_w.begin());
-          const int ic1 = (int)(std::lower_bound(copy_w.begin(), copy_w.end(), w0 + nw) - copy_w.begin());
-          if (ic1 > ic0) {
-            copy_rows<<<dim3(ic1 - ic0), dim3(256), 0, st>>>(y, pr->y_alt, h->copy_w_d + ic0,
-                                                             win_row ? h->win_row_d : nullptr, row_base);
-            if ((rc = check_launch("copy_rows"))) return rc;
-          }
-        }
-      } else if (nw > 0) {
-        const int4 phi = make_int4(ph_idx[0], ph_idx[1], ph_idx[2], ph_idx[3]);
-        const long long row_base = (long long)sd * strand_rows;
-        const int* widx = pr ? h->fc_perm_d + (size_t)sd * n_win + w0 : nullptr;   // FC row order
-        // windows of this chunk holding the SNV (alt FC: the first n_alt FC rows, widx order) and
-        // the others (copies of the ref rows)
-        int n_alt = 0, ic0 = 0, ic1 = 0;
-        if (pr) {
-          n_alt = (int)(std::lower_bound(alt_w.begin(), alt_w.end(), w0 + nw) -
-                        std::lower_bound(alt_w.begin(), alt_w.end(), w0));
-          ic0 = (int)(std::lower_bound(copy_w.begin(), copy_w.end(), w0) - copy_w.begin());
-          ic1 = (int)(std::lower_bound(copy_w.begin(), copy_w.end(), w0 + nw) - copy_w.begin());
-        }
-        // FC1 slices of <= max_batch rows (the FC1 workspace); the alt FC of a slice's alt rows
-        // reuses that slice's ref partials, so it runs right after the slice's ref FC1.  FC2
-        // unsplit: the slices' h1 rows (and FC2 output rows) gather into one FC2 launch of up to
-        // fc2_rows rows (split FC2: per slice)
-        const bool gather2 = h->fc2_splits == 1;
-        int pend = 0;   // gathered h1 rows awaiting FC2
-        auto flush2 = [&]() -> int {
-          const int n2 = pend;
-          pend = 0;
-          return n2 ? run_fc2(h, h->h1, n2, y, st, h->c_rows) : EXPECTO_OK;
-        };
-        for (int f0 = 0; f0 < nw; f0 += h->max_batch) {
-          const int fn = std::min(h->max_batch, nw - f0);
-          if (gather2 && pend + fn > h->fc2_rows && (rc = flush2())) return rc;
-          long long* crow = h->c_rows + (gather2 ? pend : 0);
-          seg_a_rows<<<dim3((fn + 255) / 256), dim3(256), 0, st>>>(
-              h->win_seg_d, h->win_off_d, win_row ? h->win_row_d : nullptr, widx ? widx + f0 : nullptr, w0 + f0,
-              fn, s0, is_rc ? 1 : 0, L, n_ph, phi, g.T6, row_base, h->a_rows, crow);
-          if ((rc = check_launch("seg_a_rows"))) return rc;
-          if (gather2) {
-            if ((rc = run_fc1(h, h->P, h->a_rows, fn, h1_rows(h, pend), st))) return rc;
-            pend += fn;
-          } else if ((rc = run_fc(h, h->P, h->a_rows, fn, y, st, h->c_rows))) {
+        EXPECTO_REQUIRE(i1 - i0 <= (size_t)cap, "a Karatsuba FC1 window group exceeds the FC1 slice");
+        const int fn = (int)(i1 - i0);
+        std::vector<long long> grows;
+        std::vector<int> prow, rgrp, ginfo;
+        FkProducts prd{h->fk_grows, {}, {}, {}};
+        fk_slice_tables(ws, (int)i0, (int)i1, g.T6, grows, prd, prow, &rgrp, &ginfo);
+        if ((rc = stage_copies(h, {{h->fk_grows, grows.data(), grows.size() * sizeof(long long)},
+                                   {h->fk_prow, prow.data(), prow.size() * sizeof(int)}}, st)))
+          return rc;
+        seg_a_rows<<<dim3((fn + 255) / 256), dim3(256), 0, st>>>(
+            h->win_seg_d, h->win_off_d, win_row ? h->win_row_d : nullptr, perm + i0, 0, fn, s0, ss, L, n_ph, phi,
+            g.T6, h->fk_arows, h->fk_crows);
+        if ((rc = check_launch("seg_a_rows")) ||
+            (rc = fk_fc1(h, h->P, h->fk_seq, prd, h->fk_arows, fn, h->fk_prow, h->fk_h1, st, nullptr, 0, h->fk_part,
+                         kFkParts * cap)))
+          return rc;
+        for (int r0 = 0; r0 < fn; r0 += h->max_batch)   // FC2 over its workspace's max_batch rows at a time
+          if ((rc = run_fc2(h, h->fk_h1 + (long long)r0 * kHidLd, std::min(h->max_batch, fn - r0), y, st,
+                            h->fk_crows + r0)))
             return rc;
+        // the slice's first groups holding alt windows (the alt groups lead the chunk's order, so
+        // they fill the first slices) and their windows
+        int n_ag = 0;
+        size_t nw_pre = 0;
+        for (size_t i = i0; has_alt && i < i1; ++i) {
+          bool galt = false;
+          size_t j = i;
+          for (; j < i1 && fk_same_group(ws[j], ws[i]); ++j) galt |= fk_is_alt(ws[j].w);
+          if (!galt) break;
+          ++n_ag;
+          nw_pre = j - i0;
+          i = j - 1;
+        }
+        if (n_ag > 0) {
+          FkProducts pa = prd;   // the alt groups' prefix of every product list, in the ref layout
+          FkMaskDesc md{};
+          for (int gq = 0; gq < 9; ++gq) {
+            int c = 0;
+            for (int i = 0; i < prd.cnt[gq]; ++i)
+              if (rgrp[prd.off[gq] + i] < n_ag) ++c;
+            pa.cnt[gq] = c;
+            pa.lay[gq] = prd.cnt[gq];
+            for (int sb = 0; prd.cnt[gq] > 0 && sb < kFkSlabs; ++sb) {
+              md.g[md.n] = gq;
+              md.s[md.n] = sb;
+              md.off[md.n] = prd.off[gq];
+              md.cnt[md.n] = c;
+              ++md.n;
+            }
           }
-          const int na = std::min(n_alt - f0, fn);   // alt rows of this slice: [f0, f0 + na)
-          if (na <= 0) continue;
-          if (f0 == 0) {
+          md.nw = (int)nw_pre;
+          std::vector<int> winfo, aperm, aprow;
+          for (size_t i = 0; i < nw_pre; ++i) {
+            winfo.push_back(ws[i0 + i].blk);
+            winfo.push_back(ws[i0 + i].off6);
+            if (fk_is_alt(ws[i0 + i].w)) {
+              aperm.push_back(ws[i0 + i].w);
+              aprow.insert(aprow.end(), prow.begin() + (long long)i * kFkParts, prow.begin() + (long long)(i + 1) * kFkParts);
+            }
+          }
+          const int na = (int)aperm.size();
+          const int tiles = (int)(cap / 256 + 1);
+          if ((rc = stage_copies(h, {{h->fk_rgrp, rgrp.data(), rgrp.size() * sizeof(int)},
+                                     {h->fk_ginfo, ginfo.data(), ginfo.size() * sizeof(int)},
+                                     {h->fk_winfo, winfo.data(), winfo.size() * sizeof(int)},
+                                     {h->fk_aperm, aperm.data(), aperm.size() * sizeof(int)},
+                                     {h->fk_aprow, aprow.data(), aprow.size() * sizeof(int)}}, st)))
+            return rc;
+          if (!alt_ready) {
             if ((rc = st_wait(h->pev[13]))) return rc;   // alt conv6 runs (and the Q reads of their patches)
-            // alt conv6 blocks into Q (conv5 rows are dead): only the rows the alt windows read
             seg_alt_blocks<<<dim3(kAltRows6, (unsigned)nb), dim3(64), 0, st>>>(h->P, h->D0, n_ph, g.T6, h->seg_tab,
                                                                               640 * eb / 16, h->Q);
             if ((rc = check_launch("seg_alt_blocks"))) return rc;
+            DeltaScope ds(h);
+            if ((rc = fk_sequences(h, h->Q, nb, g.T6, g.T6, h->seg_tab, n_ph, st, h->fk_gres, 1))) return rc;
+            alt_ready = true;
           }
-          long long* acrow = gather2 ? h->c_rows + h->fc2_rows : h->c_rows;   // alt rows apart
-          seg_a_rows<<<dim3((na + 255) / 256), dim3(256), 0, st>>>(
-              h->win_seg_d, h->win_off_d, win_row ? h->win_row_d : nullptr, widx + f0, 0, na, s0, is_rc ? 1 : 0,
-              L, n_ph, phi, g.T6, row_base, h->a_rows, acrow);
-          if ((rc = check_launch("seg_a_rows"))) return rc;
-          const unsigned* mask = nullptr;
-          double frac = 1.0;
-          if (planes_gemm()) {
-            const int tiles = (int)((na + gemm_bm() - 1) / gemm_bm());
-            unsigned* md = reinterpret_cast<unsigned*>(h->slab_mask);
-            EXPECTO_HIP_CHECK(hipMemsetAsync(md, 0, tiles * sizeof(unsigned), st));
-            fc1_slab_mask_seg<<<dim3((na + 255) / 256), dim3(256), 0, st>>>(
-                widx + f0, na, h->win_seg_d, h->win_off_d, s0, is_rc ? 1 : 0, L, phi, h->seg_tab, (int)gemm_bm(),
-                kFc1In / h->fc_splits, md);
-            if ((rc = check_launch("fc1_slab_mask_seg"))) return rc;
-            mask = md;
-            if (h->profiling) {   // executed share of the slabs, counted on the device (no sync)
-              if ((rc = count_slab_macs(h, md, tiles, na, st))) return rc;
-              frac = 0.0;
-            }
+          EXPECTO_HIP_CHECK(hipMemsetAsync(h->fk_smask, 0, (size_t)(md.n + 1) * tiles * sizeof(unsigned), st));
+          int rows_max = md.nw;
+          for (int i = 0; i < md.n; ++i) rows_max = std::max(rows_max, md.cnt[i]);
+          if (rows_max > 0) {
+            fk_seg_mask<<<dim3((rows_max + 255) / 256, md.n + 1), dim3(256), 0, st>>>(
+                md, h->fk_rgrp, h->fk_ginfo, h->fk_winfo, h->seg_tab, n_ph, make_int4(0, 0, 0, 0), tiles, h->fk_smask);
+            if ((rc = check_launch("fk_seg_mask"))) return rc;
           }
           DeltaScope ds(h);
-          if (gather2) {
-            float* h1a = h1_rows(h, h->fc2_rows);
-            if ((rc = run_fc1(h, h->Q, h->a_rows, na, h1a, st, mask, frac, fn)) ||
-                (rc = run_fc2(h, h1a, na, pr->y_alt, st, acrow)))
-              return rc;
-          } else if ((rc = run_fc(h, h->Q, h->a_rows, na, pr->y_alt, st, h->c_rows, mask, frac, fn))) {
+          if ((rc = fk_fc1(h, h->Q, h->fk_aseq, pa, h->fk_arows, (int)nw_pre, nullptr, h->fk_h1, st, h->fk_smask, tiles,
+                           h->fk_part, kFkParts * cap)) ||
+              (na > 0 && (rc = fk_reduce(h, h->fk_part, h->fk_aprow, na, h->fk_h1, st))))
             return rc;
+          if (na > 0) {
+            seg_a_rows<<<dim3((na + 255) / 256), dim3(256), 0, st>>>(
+                h->win_seg_d, h->win_off_d, win_row ? h->win_row_d : nullptr, h->fk_aperm, 0, na, s0, ss, L, n_ph,
+                phi, g.T6, h->fk_arows, h->fk_crows);
+            if ((rc = check_launch("seg_a_rows"))) return rc;
+            for (int r0 = 0; r0 < na; r0 += h->max_batch)
+              if ((rc = run_fc2(h, h->fk_h1 + (long long)r0 * kHidLd, std::min(h->max_batch, na - r0), pr->y_alt, st,
+                                h->fk_crows + r0)))
+                return rc;
           }
         }
-        if ((rc = flush2())) return rc;   // the ref rows are read by copy_rows below
-        if (pr) {
-          if (ic1 > ic0) {
-            copy_rows<<<dim3(ic1 - ic0), dim3(256), 0, st>>>(y, pr->y_alt, h->copy_w_d + ic0,
-                                                             win_row ? h->win_row_d : nullptr, row_base);
-            if ((rc = check_launch("copy_rows"))) return rc;
-          }
+        i0 = i1;
+      }
+      if (pr) {
+        const int ic0 = (int)(std::lower_bound(copy_w.begin(), copy_w.end(), w0) - copy_w.begin());
+        const int ic1 = (int)(std::lower_bound(copy_w.begin(), copy_w.end(), w0 + nw) - copy_w.begin());
+        if (ic1 > ic0) {
+          copy_rows<<<dim3(ic1 - ic0), dim3(256), 0, st>>>(y, pr->y_alt, h->copy_w_d + ic0,
+                                                           win_row ? h->win_row_d : nullptr, n_win, ss.rc_rows);
+          if ((rc = check_launch("copy_rows"))) return rc;
         }
       }
-      if (pr && (rc = st_wait(h->pev[13]))) return rc;   // every alt run of the chunk joined
+    } else if (nw > 0) {
+      const int4 phi = make_int4(ph_idx[0], ph_idx[1], ph_idx[2], ph_idx[3]);
+      const int* widx = pr ? h->fc_perm_d + w0 : nullptr;   // FC row order
+      // windows of this chunk holding the SNV (alt FC: the first n_alt FC rows, widx order) and
+      // the others (copies of the ref rows)
+      int n_alt = 0, ic0 = 0, ic1 = 0;
+      if (pr) {
+        n_alt = (int)(std::lower_bound(alt_w.begin(), alt_w.end(), w0 + nw) -
+                      std::lower_bound(alt_w.begin(), alt_w.end(), w0));
+        ic0 = (int)(std::lower_bound(copy_w.begin(), copy_w.end(), w0) - copy_w.begin());
+        ic1 = (int)(std::lower_bound(copy_w.begin(), copy_w.end(), w0 + nw) - copy_w.begin());
+      }
+      // FC1 slices of <= max_batch rows (the FC1 workspace); the alt FC of a slice's alt rows
+      // reuses that slice's ref partials, so it runs right after the slice's ref FC1.  FC2
+      // unsplit: the slices' h1 rows (and FC2 output rows) gather into one FC2 launch of up to
+      // fc2_rows rows (split FC2: per slice)
+      const bool gather2 = h->fc2_splits == 1;
+      int pend = 0;   // gathered h1 rows awaiting FC2
+      auto flush2 = [&]() -> int {
+        const int n2 = pend;
+        pend = 0;
+        return n2 ? run_fc2(h, h->h1, n2, y, st, h->c_rows) : EXPECTO_OK;
+      };
+      for (int f0 = 0; f0 < nw; f0 += h->max_batch) {
+        const int fn = std::min(h->max_batch, nw - f0);
+        if (gather2 && pend + fn > h->fc2_rows && (rc = flush2())) return rc;
+        long long* crow = h->c_rows + (gather2 ? pend : 0);
+        seg_a_rows<<<dim3((fn + 255) / 256), dim3(256), 0, st>>>(
+            h->win_seg_d, h->win_off_d, win_row ? h->win_row_d : nullptr, widx ? widx + f0 : nullptr, w0 + f0,
+            fn, s0, ss, L, n_ph, phi, g.T6, h->a_rows, crow);
+        if ((rc = check_launch("seg_a_rows"))) return rc;
+        if (gather2) {
+          if ((rc = run_fc1(h, h->P, h->a_rows, fn, h1_rows(h, pend), st))) return rc;
+          pend += fn;
+        } else if ((rc = run_fc(h, h->P, h->a_rows, fn, y, st, h->c_rows))) {
+          return rc;
+        }
+        const int na = std::min(n_alt - f0, fn);   // alt rows of this slice: [f0, f0 + na)
+        if (na <= 0) continue;
+        if (f0 == 0) {
+          if ((rc = st_wait(h->pev[13]))) return rc;   // alt conv6 runs (and the Q reads of their patches)
+          // alt conv6 blocks into Q (conv5 rows are dead): only the rows the alt windows read
+          seg_alt_blocks<<<dim3(kAltRows6, (unsigned)nb), dim3(64), 0, st>>>(h->P, h->D0, n_ph, g.T6, h->seg_tab,
+                                                                            640 * eb / 16, h->Q);
+          if ((rc = check_launch("seg_alt_blocks"))) return rc;
+        }
+        long long* acrow = gather2 ? h->c_rows + h->fc2_rows : h->c_rows;   // alt rows apart
+        seg_a_rows<<<dim3((na + 255) / 256), dim3(256), 0, st>>>(
+            h->win_seg_d, h->win_off_d, win_row ? h->win_row_d : nullptr, widx + f0, 0, na, s0, ss, L, n_ph, phi,
+            g.T6, h->a_rows, acrow);
+        if ((rc = check_launch("seg_a_rows"))) return rc;
+        const unsigned* mask = nullptr;
+        double frac = 1.0;
+        if (planes_gemm()) {
+          const int tiles = (int)((na + gemm_bm() - 1) / gemm_bm());
+          unsigned* md = reinterpret_cast<unsigned*>(h->slab_mask);
+          EXPECTO_HIP_CHECK(hipMemsetAsync(md, 0, tiles * sizeof(unsigned), st));
+          fc1_slab_mask_seg<<<dim3((na + 255) / 256), dim3(256), 0, st>>>(
+              widx + f0, na, h->win_seg_d, h->win_off_d, s0, ss, L, phi, h->seg_tab, (int)gemm_bm(),
+              kFc1In / h->fc_splits, md);
+          if ((rc = check_launch("fc1_slab_mask_seg"))) return rc;
+          mask = md;
+          if (h->profiling) {   // executed share of the slabs, counted on the device (no sync)
+            if ((rc = count_slab_macs(h, md, tiles, na, st))) return rc;
+            frac = 0.0;
+          }
+        }
+        DeltaScope ds(h);
+        if (gather2) {
+          float* h1a = h1_rows(h, h->fc2_rows);
+          if ((rc = run_fc1(h, h->Q, h->a_rows, na, h1a, st, mask, frac, fn)) ||
+              (rc = run_fc2(h, h1a, na, pr->y_alt, st, acrow)))
+            return rc;
+        } else if ((rc = run_fc(h, h->Q, h->a_rows, na, pr->y_alt, st, h->c_rows, mask, frac, fn))) {
+          return rc;
+        }
+      }
+      if ((rc = flush2())) return rc;   // the ref rows are read by copy_rows below
+      if (pr) {
+        if (ic1 > ic0) {
+          copy_rows<<<dim3(ic1 - ic0), dim3(256), 0, st>>>(y, pr->y_alt, h->copy_w_d + ic0,
+                                                           win_row ? h->win_row_d : nullptr, n_win, ss.rc_rows);
+          if ((rc = check_launch("copy_rows"))) return rc;
+        }
+      }
     }
+    if (pr && (rc = st_wait(h->pev[13]))) return rc;   // every alt run of the chunk joined
   }
   return EXPECTO_OK;
 }
@@ -3830,6 +3849,7 @@ int expecto_beluga_create(int device, const float* const* params, int max_batch,
     h->fk_role = v;
   }
   if (const char* e = getenv("EXPECTO_SEG_CHUNK_WINDOWS")) h->seg_chunk_windows = atoi(e);   // same bits either way
+  if (const char* e = getenv("EXPECTO_SEG_MERGE_STRANDS")) h->seg_merge_strands = atoi(e) != 0;   // same bits either way
   if (const char* e = getenv("EXPECTO_CONV_NARROW")) {   // conv5 / conv6 tile width (same bits either way)
     const int v = atoi(e);
     EXPECTO_REQUIRE(v >= -1 && v <= 1, "EXPECTO_CONV_NARROW must be -1 (auto), 0 or 1");
@@ -3865,6 +3885,9 @@ int expecto_beluga_create(int device, const float* const* params, int max_batch,
     if ((rc = dalloc(h, &rows, (size_t)(max_batch + h1_rows) * 2))) return fail(rc);
     h->a_rows = reinterpret_cast<long long*>(rows);
     h->c_rows = h->a_rows + max_batch;
+    float* gr = nullptr;
+    if ((rc = dalloc(h, &gr, (size_t)kGresPerBatch * max_batch))) return fail(rc);
+    h->fk_gres = reinterpret_cast<int*>(gr);
   }
   EXPECTO_HIP_CHECK(hipMemsetAsync(h->P, 0, act_alloc(pf) * sizeof(float), st));
   EXPECTO_HIP_CHECK(hipMemsetAsync(h->Q, 0, act_alloc(qf) * sizeof(float), st));
@@ -3891,7 +3914,6 @@ void expecto_beluga_destroy(expecto_beluga_t h) {
     if (p) (void)hipFree(p);
   for (float* p : h->fk_aseq)
     if (p) (void)hipFree(p);
-  if (h->fk_gres) (void)hipFree(h->fk_gres);
   if (h->seam) (void)hipFree(h->seam);
   if (h->edge) (void)hipFree(h->edge);
   for (void* p : h->allocs) (void)hipFree(p);
