@@ -310,9 +310,12 @@ __global__ void variant_reduce_kernel(const float* __restrict__ eff, const long 
   __syncthreads();
   const int f = blockIdx.x * blockDim.x + threadIdx.x;
   if (f >= nfeat) return;
+  // predict.py:123 reduces with x + y from the first shift's term, not from +0.0: a sum whose
+  // terms are all -0.0 (negative effects under a masked, zero weight) is -0.0.  -0.0 + x == x for
+  // every x, so the sums start there (all three variant kernels).
   double acc[10];
 #pragma unroll
-  for (int k = 0; k < 10; ++k) acc[k] = 0.0;
+  for (int k = 0; k < 10; ++k) acc[k] = -0.0;
   for (int j = 0; j < n_shift; ++j) {
     const double e = (double)eff[((long long)j * n + v) * nfeat + f];
 #pragma unroll
@@ -359,7 +362,7 @@ __global__ void variant_reduce2_kernel(const float* __restrict__ eff, const long
   if (f >= nfeat) return;
   double a0[10], a1[10];
 #pragma unroll
-  for (int k = 0; k < 10; ++k) a0[k] = a1[k] = 0.0;
+  for (int k = 0; k < 10; ++k) a0[k] = a1[k] = -0.0;   // the first term as it is (variant_reduce_kernel)
   for (int j = 0; j < n_shift; ++j) {
     const float2 e2 = *reinterpret_cast<const float2*>(eff + ((long long)j * n + v) * nfeat + f);
     const double e0 = (double)e2.x, e1 = (double)e2.y;
@@ -399,7 +402,7 @@ __global__ __launch_bounds__(kRowsPairs) void variant_reduce_rows_kernel(
   __syncthreads();
   double a0[10], a1[10];
 #pragma unroll
-  for (int k = 0; k < 10; ++k) a0[k] = a1[k] = 0.0;
+  for (int k = 0; k < 10; ++k) a0[k] = a1[k] = -0.0;   // the first term as it is (variant_reduce_kernel)
   if (t < np) {
     const int f = 2 * (pb + t);
     for (int j = 0; j < n_shift; ++j) {

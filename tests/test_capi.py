@@ -60,6 +60,39 @@ def test_host_only_calls(lib):
     assert lib.expecto_variant_windows(None, 0, None, None, None, 1, None, 0, None, None) == -1
 
 
+def test_argument_limits_are_refused_before_any_launch(lib):
+    """The grid's y limit (65535 items per call) and the reductions' LDS limit (819 shifts): each
+    entry point refuses one more with EXPECTO_EINVAL and its own message, before it looks at a
+    pointer or launches anything."""
+    n = 65536
+    calls = [
+        (lambda: lib.expecto_variant_windows(None, 0, None, None, None, n, None, 9, None, None), "65535 variants"),
+        (lambda: lib.expecto_indel_windows(None, 0, None, None, None, None, None, None, None, n, None, None),
+         "65535 indel windows"),
+        (lambda: lib.expecto_tss_windows(None, 0, None, None, n, None, 200, None, None), "65535 genes"),
+        (lambda: lib.expecto_gather_segments(None, 0, None, n, 2000, None, None, None, None), "65535 segments"),
+        (lambda: lib.expecto_tss_reduce(None, None, None, n, 200, 2002, None, None), "65535 genes"),
+        (lambda: lib.expecto_variant_reduce(None, None, None, None, 9, n, 2002, None, None), "65535 variants"),
+        (lambda: lib.expecto_variant_reduce_lut(None, None, None, None, 9, n, 2002, None, 0, None, None),
+         "65535 variants"),
+        (lambda: lib.expecto_shift_reduce(None, None, None, n, 200, 2002, 3, None, None), "65535 sequences"),
+        (lambda: lib.expecto_tss_reduce(None, None, None, 1, 820, 2002, None, None), "n_shift <= 819"),
+        (lambda: lib.expecto_variant_reduce(None, None, None, None, 820, 1, 2002, None, None), "n_shift <= 819"),
+        (lambda: lib.expecto_variant_reduce_lut(None, None, None, None, 820, 1, 2002, None, 0, None, None),
+         "n_shift <= 819"),
+        (lambda: lib.expecto_shift_reduce(None, None, None, 1, 820, 2002, 3, None, None), "n_shift <= 819"),
+        (lambda: lib.expecto_variant_windows(None, 0, None, None, None, 1, None, 32768, None, None), "shift count"),
+    ]
+    for k, (call, text) in enumerate(calls):
+        lib.expecto_diff(None, None, -1, None, None)             # another message in between
+        assert "negative count" in lib.expecto_last_error().decode()
+        assert call() == -1, k
+        assert text in lib.expecto_last_error().decode(), (k, lib.expecto_last_error())
+    # one fewer passes the limit and fails on the null pointers instead
+    assert lib.expecto_tss_reduce(None, None, None, 65535, 819, 2002, None, None) == -1
+    assert "null argument" in lib.expecto_last_error().decode()
+
+
 def test_no_cpu_fallback_without_library(tmp_path, monkeypatch):
     from expecto_amd import _lib
     monkeypatch.setattr(_lib, "_lib", None)
