@@ -33,10 +33,12 @@
 
 #include "common.h"
 #include "gemm_kernel.h"
+#include "seg_plan.h"
 
 namespace expecto {
 
-constexpr int kLen = 2000;         // input window (chromatin.py:35-36, fixed by FC1)
+static_assert(kStrandFwd == EXPECTO_STRAND_FWD && kStrandRc == EXPECTO_STRAND_RC && kStrandBoth == EXPECTO_STRAND_BOTH &&
+              EXPECTO_EINVAL == -1, "seg_plan.h restates the strand modes and the refusal code");
 constexpr int kNFeat = 2002;
 constexpr int kFc1In = 67840;      // 640 * 106
 constexpr int kFc1Out = 2003;
@@ -453,16 +455,6 @@ __global__ __launch_bounds__(256) void pool4_phases_h2m(const float* __restrict_
     *reinterpret_cast<halfx8*>(dst + 64) = ol;
   }
 }
-
-// Strands of a segment call.  Its chunks run over (strand, segment) entries e, the fwd entries first:
-// entry e is segment e - n_seg if e >= n_seg, else e, on the rc strand iff e >= rc_ent.  Its windows
-// are numbered the same way: v is window v - n_win if v >= n_win (its rows then rc_rows further
-// on in the output), else v, on the rc strand iff v >= rc_win.  (FWD: rc_* past every index; RC: 0;
-// BOTH: n_seg / n_win.)
-struct SegStrands {
-  int n_seg, rc_ent, n_win, rc_win;
-  long long rc_rows;
-};
 
 // FC1 row table of the windows of one segment chunk: window m of the chunk reads conv6
 // rows [off6, off6+106) of block (entry - ent_base, pool2 phase).
@@ -2687,23 +2679,6 @@ int fk_fc1(expecto_beluga* h, const float* x, float* const* seq, const FkProduct
   return prow ? fk_reduce(h, part, prow, n, h1, st) : EXPECTO_OK;
 }
 
-// A window of the segment path for the Karatsuba FC1 (w: its number; off: its offset in its segment,
-// chunk block `seg`, strand rc): its conv6 block (seg, pool2 phase) and
-// offset in conv6 rows (as seg_a_rows computes them); its role is its 25-row step mod 4 and its
-// group the windows of its block with the same group start off6 - 25 role.
-struct FkWin {
-  int w, blk, off6;
-};
-int fk_role_of(int off6) { return (off6 / 25) & 3; }
-FkWin fk_win(int w, int seg, int off, bool rc, int L, int n_ph, const int* ph_idx) {
-  const int o = rc ? L - kLen - off : off;
-  const int q = o >> 2, p = q & 3;
-  return {w, seg * n_ph + ph_idx[p], (q - p) >> 2};
-}
-bool fk_same_group(const FkWin& a, const FkWin& b) {
-  return a.blk == b.blk && a.off6 - 25 * fk_role_of(a.off6) == b.off6 - 25 * fk_role_of(b.off6);
-}
-
 // Tables of windows ws[i0, i1) (whole groups, group order) for fk_fc1: per product the starts of
 // the groups that need it (element offsets into the block rows, T6 rows per block) and each
 // window's partial rows, in fk_fc1's descriptor order (products, slabs, then the tail).
@@ -2717,14 +2692,14 @@ void fk_slice_tables(const std::vector<FkWin>& ws, int i0, int i1, int T6, std::
   for (int i = i0; i < i1; ++i) {
     const FkWin& w = ws[i];
     if (i == i0 || !fk_same_group(w, ws[i - 1])) {
-      gst.push_back(((long long)w.blk * T6 + w.off6 - 25 * fk_role_of(w.off6)) * 640);
+      gst.push_back(((long long)w.blk * T6 + fk_group_of(w.off6)) * 640);
       need.push_back(0u);
     }
     gi[i - i0] = (int)gst.size() - 1;
     for (int j = 0; j < 4; ++j) need.back() |= 1u << kFkRole[fk_role_of(w.off6)][j];
     if (ginfo && gi[i - i0] * 2 == (int)ginfo->size()) {   // (block, start row) of a new group
       ginfo->push_back(w.blk);
-      ginfo->push_back(w.off6 - 25 * fk_role_of(w.off6));
+      ginfo->push_back(fk_group_of(w.off6));
     }
   }
   const int ng = (int)gst.size();
@@ -2858,36 +2833,6 @@ int ensure_delta(expecto_beluga* h) {
 }
 
 // ---- segment path: windows that are slices of longer sequences share the trunk --------
-// A segment of L codes (L % 4 == 0); a window at offset o (o % 4 == 0, o + 2000 <= L).
-// conv1..conv4 run once over the segment; pool1 is fused into conv2 (phase 0 serves every
-// window since o % 4 == 0); pool2 runs separately for each phase p = (o/4) % 4 present;
-// conv5/conv6 run per (segment, phase) block; FC1 reads each window's 106 conv6 rows
-// through a row table.  Every per-window output element is computed with the same operands
-// and K order as the per-window path, so results are bit-identical to it.
-struct SegGeo {
-  int L, T1, S1, P1, T3, T4, S5, T5, T6;
-  size_t p_rows_floats, q_rows_floats;  // per segment, given n_ph phases
-};
-
-SegGeo seg_geo(int L, int n_ph) {
-  SegGeo g{};
-  g.L = L;
-  g.T1 = L - 7;
-  g.S1 = (g.T1 + 3) / 4 * 4;
-  g.P1 = (g.T1 - 7) / 4;
-  g.T3 = g.P1 - 7;
-  g.T4 = g.T3 - 7;
-  g.S5 = g.T4 / 4;        // rows of the phase-0 pool2 block (the longest)
-  g.T5 = g.S5 - 7;
-  g.T6 = g.T5 - 7;
-  const size_t p_conv1 = (size_t)g.S1 * 320, p_conv3 = (size_t)((g.T3 + 3) & ~3) * 480, p_pool2 = (size_t)n_ph * g.S5 * 480,
-               p_conv6 = (size_t)n_ph * g.T6 * 640;
-  const size_t q_pool1 = (size_t)g.P1 * 320, q_conv4 = (size_t)g.T4 * 480, q_conv5 = (size_t)n_ph * g.T5 * 640;
-  g.p_rows_floats = std::max(std::max(p_conv1, p_conv3), std::max(p_pool2, p_conv6));
-  g.q_rows_floats = std::max(q_pool1, std::max(q_conv4, q_conv5));
-  return g;
-}
-
 // Segment pairs: the alt segment s is segment s with code alt_code[s] (DEVICE) at var_pos[s]
 // (HOST); its windows (the same offsets) go to y_alt.  Windows that hold the SNV get their
 // alt trunk through per-layer alt runs and their own FC; the others equal their ref window
@@ -2899,39 +2844,429 @@ struct SegPairs {
   long long strand_stride;
 };
 
+// One forward_segments call as its stage functions see it (the plan: seg_plan.h), and one chunk of it.
+struct SegCall {
+  expecto_beluga* h;
+  const SegPlan& pl;
+  hipStream_t st, sa;      // sa: the alt runs of segment pairs (the handle's second stream, or st)
+  const SegPairs* pr;
+  SegDims gd;
+  int4 ph4, phi;
+  int eb;
+  const uint8_t* codes;
+  long long code_stride;
+  int mode;
+  float* y;
+  const int* win_row_d;    // the staged win_row, or null
+};
+struct SegChunk {
+  size_t ci;
+  int s0, ns, w0, nw;      // entries [s0, s0 + ns), windows [w0, w0 + nw)
+  long long nb;            // (segment, phase) blocks
+};
+// P and Q trade roles after the fused pool2 (seg_trunk) for the rest of the chunk.  The guard lives
+// in forward_segments' chunk loop, around every stage of the chunk, so the swap is undone at the end
+// of the chunk and on every early return, a stage function's included.
+struct PQSwap {
+  expecto_beluga* h;
+  bool on;
+  ~PQSwap() {
+    if (on) std::swap(h->P, h->Q);
+  }
+};
+
+// Stream `to` waits for what stream `from` holds so far (one stream: nothing to order).
+int stream_order(hipStream_t from, hipStream_t to, hipEvent_t e) {
+  if (from == to) return EXPECTO_OK;
+  EXPECTO_HIP_CHECK(hipEventRecord(e, from));
+  EXPECTO_HIP_CHECK(hipStreamWaitEvent(to, e, 0));
+  return EXPECTO_OK;
+}
+
+// Alt runs (segment pairs) on the handle's second stream `sa`: the alt input patch of
+// layer l is assembled from the ref input of layer l (`ref`, ref_rows per block; the
+// ref layer l reads it concurrently) and the previous alt run, then the layer's GEMM runs
+// on it beside the next ref layers.  The ref launch that next overwrites `ref` (ping-
+// pong) waits for the assembly (event `done`).  Same kernels, K order and weights.
+int seg_alt_asm(const SegCall& c, const SegChunk& ck, int l, const float* ref, int ref_rows, const float* dprev,
+                int wprev, int nbk, int ib, int mult, int irp, int arows, hipEvent_t ready, hipEvent_t done) {
+  int rc;
+  if ((rc = stream_order(c.st, c.sa, ready))) return rc;
+  const int row16 = kConv[l].cin * c.eb / 16;
+  seg_delta_assemble<<<dim3(ck.ns * nbk), dim3(256), 0, c.sa>>>(ref, ref_rows, dprev, wprev, c.h->seg_tab, nbk, ib,
+                                                                 mult, irp, arows, row16, c.h->DA);
+  rc = check_launch("seg_delta_assemble");
+  if (!rc && c.sa != c.st) EXPECTO_HIP_CHECK(hipEventRecord(done, c.sa));
+  return rc;
+}
+int seg_alt_gemm(const SegCall& c, const SegChunk& ck, int l, int nbk, int arows, int w, bool pool, float* dnext) {
+  DeltaScope ds(c.h);
+  return run_conv(c.h, l, c.h->DA, dnext, (long long)ck.ns * nbk, arows, w, w, pool, c.sa);
+}
+int seg_st_wait(const SegCall& c, hipEvent_t e) {   // st: the alt work recorded in e is done
+  if (c.sa != c.st) EXPECTO_HIP_CHECK(hipStreamWaitEvent(c.st, e, 0));
+  return EXPECTO_OK;
+}
+
+// FC1 row table and output rows of n windows of the chunk: widx[0, n), or windows w0 .. w0 + n - 1
+int seg_rows(const SegCall& c, const SegChunk& ck, const int* widx, int w0, int n, long long* a_rows,
+             long long* c_rows) {
+  seg_a_rows<<<dim3((n + 255) / 256), dim3(256), 0, c.st>>>(c.h->win_seg_d, c.h->win_off_d, c.win_row_d, widx, w0, n,
+                                                             ck.s0, c.pl.ss, c.pl.g.L, c.pl.n_ph, c.phi, c.pl.g.T6,
+                                                             a_rows, c_rows);
+  return check_launch("seg_a_rows");
+}
+
+// FC2 of n h1 rows over its workspace's max_batch rows at a time
+int seg_fc2(const SegCall& c, const float* h1, int n, float* y, const long long* c_rows) {
+  int rc;
+  for (int r0 = 0; r0 < n; r0 += c.h->max_batch)
+    if ((rc = run_fc2(c.h, h1 + (long long)r0 * kHidLd, std::min(c.h->max_batch, n - r0), y, c.st, c_rows + r0)))
+      return rc;
+  return EXPECTO_OK;
+}
+
+// The alt conv6 blocks of the chunk into Q (conv5 rows are dead): only the rows the alt windows
+// read, once the alt conv6 runs (and the Q reads of their patches) are done
+int seg_alt_conv6(const SegCall& c, const SegChunk& ck) {
+  int rc;
+  if ((rc = seg_st_wait(c, c.h->pev[13]))) return rc;
+  seg_alt_blocks<<<dim3(kAltRows6, (unsigned)ck.nb), dim3(64), 0, c.st>>>(c.h->P, c.h->D0, c.pl.n_ph, c.pl.g.T6,
+                                                                           c.h->seg_tab, 640 * c.eb / 16, c.h->Q);
+  return check_launch("seg_alt_blocks");
+}
+
+// Segment pairs: the chunk's windows without the SNV get their ref rows as their alt rows
+int seg_copy_tail(const SegCall& c, const SegChunk& ck) {
+  if (!c.pr) return EXPECTO_OK;
+  const std::vector<int>& cw = c.pl.copy_w;
+  const int ic0 = (int)(std::lower_bound(cw.begin(), cw.end(), ck.w0) - cw.begin());
+  const int ic1 = (int)(std::lower_bound(cw.begin(), cw.end(), ck.w0 + ck.nw) - cw.begin());
+  if (ic1 <= ic0) return EXPECTO_OK;
+  copy_rows<<<dim3(ic1 - ic0), dim3(256), 0, c.st>>>(c.y, c.pr->y_alt, c.h->copy_w_d + ic0, c.win_row_d, c.pl.ss.n_win,
+                                                      c.pl.ss.rc_rows);
+  return check_launch("copy_rows");
+}
+
+// The trunk of a chunk on the two streams: conv1 (or the k-mer table, or fused into conv2) to
+// conv6 over the chunk's entries on st, the alt runs of segment pairs beside them on sa.
+int seg_trunk(const SegCall& c, const SegChunk& ck, PQSwap& pq) {
+  expecto_beluga* h = c.h;
+  const SegPairs* pr = c.pr;
+  const SegGeo& g = c.pl.g;
+  const hipStream_t st = c.st, sa = c.sa;
+  const int s0 = ck.s0, ns = ck.ns, n_ph = c.pl.n_ph;
+  const long long nb = ck.nb;
+  int rc;
+  // sa: the previous chunk's use of the alt buffers on st is done
+  if (pr && (rc = stream_order(st, sa, h->pev[0]))) return rc;
+  // conv1 from codes: virtual rows = the chunk's entries, code rows s0.. of the call's n_seg in
+  // its strand mode (BOTH: rows >= n_seg are the rc strand's); the kernel mirrors the rc rows
+  // (fused: inside the conv2 launch)
+  const bool kmer = use_kmer(h, nullptr);
+  const bool fuse = !kmer && fuse_conv1(h, nullptr);
+  const C1Src f1{c.codes, c.code_stride, c.pl.ss.n_seg, c.mode, s0, g.L};
+  if (!kmer && !fuse &&
+      (rc = run_conv1(h, nullptr, c.codes, c.code_stride, c.pl.ss.n_seg, c.mode, s0, ns, g.L, g.S1, st)))
+    return rc;
+  if (pr) {
+    seg_delta_table<<<dim3((ns + 255) / 256), dim3(256), 0, sa>>>(h->seg_var_d, s0, ns, c.pl.ss, c.gd, n_ph, c.ph4,
+                                                                 h->seg_tab);
+    if ((rc = check_launch("seg_delta_table"))) return rc;
+    if (kmer || fuse) {   // the alt conv2 patch straight from the alt codes (k-mer table, or conv1 -> DA)
+      seg_delta_codes2<<<dim3((ns + 4) / 5), dim3(5 * kC1PatStride), 0, sa>>>(
+          c.codes, c.code_stride, pr->alt_code, s0, ns, c.pl.ss, g.L, h->seg_tab, h->delta_codes);
+      if ((rc = check_launch("seg_delta_codes2"))) return rc;
+      DeltaScope ds(h);
+      if (fuse && (rc = run_conv1(h, nullptr, h->delta_codes, kC1PatStride, ns, EXPECTO_STRAND_FWD, 0, ns, kC1Pat,
+                                  kDA[2], sa, h->DA)))
+        return rc;
+    } else {
+      seg_delta_codes<<<dim3((ns + 15) / 16), dim3(256), 0, sa>>>(c.codes, c.code_stride, pr->alt_code, s0, ns,
+                                                                 c.pl.ss, g.L, h->seg_tab, h->delta_codes);
+      if ((rc = check_launch("seg_delta_codes"))) return rc;
+      DeltaScope ds(h);
+      if ((rc = run_conv1(h, nullptr, h->delta_codes, 16, ns, EXPECTO_STRAND_FWD, 0, ns, kDA[1], kDW[1], sa, h->D0)))
+        return rc;
+    }
+  }
+  // conv2 + pool1 (P -> Q), conv3 (Q -> P), conv4 unpooled (P -> Q); alt runs D0 <-> D1
+  if (pr && !kmer && !fuse &&
+      (rc = seg_alt_asm(c, ck, 0, h->P, g.S1, h->D0, kDW[1], 1, 2, 4, 1, kDA[2], h->pev[1], h->pev[2])))
+    return rc;
+  if (kmer)
+    rc = run_conv2_kmer(h, f1, ns, g.P1, g.P1, h->Q, st);
+  else
+    rc = run_conv(h, 0, h->P, h->Q, ns, g.S1, g.P1, g.P1, true, st, fuse ? &f1 : nullptr);
+  if (rc) return rc;
+  if (pr && kmer) {   // alt pooled conv2 rows [r2, r2 + kDW[2]) of each segment into D1
+    DeltaScope ds(h);
+    const C1Src fa{h->delta_codes, kC1PatStride, ns, EXPECTO_STRAND_FWD, 0, kC1Pat};
+    if ((rc = run_conv2_kmer(h, fa, ns, kDW[2], kDW[2], h->D1, sa))) return rc;
+  } else if (pr && ((!fuse && (rc = seg_st_wait(c, h->pev[2]))) ||
+                    (rc = seg_alt_gemm(c, ck, 0, 1, kDA[2], kDW[2], true, h->D1)))) {
+    return rc;
+  }
+  if (pr && (rc = seg_alt_asm(c, ck, 1, h->Q, g.P1, h->D1, kDW[2], 1, 3, 1, 2, kDA[3], h->pev[3], h->pev[4])))
+    return rc;
+  // conv3 rows at a 4-aligned stride per segment (T3p >= T3), so conv4's rows of every segment
+  // start 4-aligned in its M index space: pool2 groups are then lane-local (epilogue_pool_ph02)
+  const int T3p = (g.T3 + 3) & ~3;
+  if ((rc = run_conv(h, 1, h->Q, h->P, ns, g.P1, g.T3, T3p, false, st))) return rc;
+  if (pr && ((rc = seg_st_wait(c, h->pev[4])) || (rc = seg_alt_gemm(c, ck, 1, 1, kDA[3], kDW[3], false, h->D0))))
+    return rc;
+  if (pr && (rc = seg_alt_asm(c, ck, 2, h->P, T3p, h->D0, kDW[3], 1, 4, 1, 3, kA4u, h->pev[5], h->pev[6])))
+    return rc;
+  // pool2 fused into conv4 (P -> phase blocks in Q, then P and Q trade roles for the rest of
+  // the chunk: conv5 Q -> P, conv6 P -> Q, ... -- both hold a chunk's conv5 / conv6 rows, see
+  // seg_geo), else conv4 unpooled (P -> Q) and a pool pass (Q -> P)
+  const bool pfused = conv4_pool_fused(h, (long long)ns * T3p, n_ph, c.pl.ph);
+  if (pfused) {
+    if ((rc = run_conv4_pool_fused(h, h->P, h->Q, ns, T3p, g.T4, g.S5, pr ? h->seg_tab : nullptr, st))) return rc;
+    std::swap(h->P, h->Q);
+    pq.on = true;
+  } else if ((rc = run_conv(h, 2, h->P, h->Q, ns, T3p, g.T4, g.T4, false, st))) {
+    return rc;
+  }
+  if (pr && ((rc = seg_st_wait(c, h->pev[6])) || (rc = seg_alt_gemm(c, ck, 2, 1, kA4u, kW4u, false, h->D1))))
+    return rc;
+  if (!pfused) {  // pool2 phases (Q -> P)
+    LayerTimer lt(h, 3, st);
+    if (act_fmt() == 2 && h->pool_one_pass) {   // all phases in one pass over the conv4 rows
+      dim3 grid((g.S5 + 3) / 4, ns);
+      pool4_phases_h2m<<<grid, dim3(256), 0, st>>>(h->Q, g.T4, g.T4, 480, n_ph, c.ph4, g.S5, h->P);
+    } else if (act_fmt() == 2) {
+      dim3 grid((g.S5 + 3) / 4, ns * n_ph);
+      pool4_phases_h2<<<grid, dim3(256), 0, st>>>(h->Q, g.T4, g.T4, 480, n_ph, c.ph4, g.S5, h->P);
+    } else {
+      dim3 grid(g.S5, ns * n_ph);
+      pool4_phases<<<grid, dim3(480), 0, st>>>(h->Q, ns, g.T4, g.T4, 480, n_ph, c.ph4, g.S5, h->P, act_fmt());
+    }
+    if ((rc = check_launch("pool4_phases"))) return rc;
+  }
+  if (pr) {   // alt pool2 phases from the unpooled conv4 rows (Q) and the alt conv4 run
+    if ((rc = stream_order(st, sa, h->pev[7]))) return rc;
+    seg_delta_pool<<<dim3(kDW[4], (unsigned)nb), dim3(480), 0, sa>>>(pfused ? h->edge : h->Q, g.T4, h->D1, n_ph,
+                                                                     c.ph4, h->seg_tab, act_fmt(), h->D0,
+                                                                     pfused ? 1 : 0);
+    if ((rc = check_launch("seg_delta_pool"))) return rc;
+    if (sa != st) EXPECTO_HIP_CHECK(hipEventRecord(h->pev[8], sa));
+    if ((rc = seg_alt_asm(c, ck, 3, h->P, g.S5, h->D0, kDW[4], n_ph, 9, 1, 5, kDA[5], h->pev[9], h->pev[10])))
+      return rc;
+    if ((rc = seg_st_wait(c, h->pev[8]))) return rc;    // conv5 overwrites Q
+  }
+  // conv5 (P -> Q), conv6 (Q -> P) over (segment, phase) blocks
+  if ((rc = run_conv(h, 3, h->P, h->Q, nb, g.S5, g.T5, g.T5, false, st))) return rc;
+  if (pr && ((rc = seg_st_wait(c, h->pev[10])) || (rc = seg_alt_gemm(c, ck, 3, n_ph, kDA[5], kDW[5], false, h->D1))))
+    return rc;
+  if (pr && (rc = seg_alt_asm(c, ck, 4, h->Q, g.T5, h->D1, kDW[5], n_ph, 13, 1, 9, kDA[6], h->pev[11], h->pev[12])))
+    return rc;
+  if ((rc = run_conv(h, 4, h->Q, h->P, nb, g.T5, g.T6, g.T6, false, st))) return rc;
+  if (pr) {
+    if ((rc = seg_alt_gemm(c, ck, 4, n_ph, kDA[6], kDW[6], false, h->D0))) return rc;
+    if (sa != st) EXPECTO_HIP_CHECK(hipEventRecord(h->pev[13], sa));   // all alt runs of the chunk
+  }
+  return EXPECTO_OK;
+}
+
+// Tables of a Karatsuba slice's in-place alt pass (host only): the alt groups' prefix of every
+// product list in the ref layout (prd, rgrp, prow: fk_slice_tables of the slice), the mask
+// descriptors, the prefix windows' (block, conv6 offset) and the alt windows with their partial rows.
+struct FkAltTables {
+  FkProducts pa;
+  FkMaskDesc md;
+  std::vector<int> winfo, aperm, aprow;
+};
+FkAltTables fk_alt_tables(const SegPlan& pl, const std::vector<FkWin>& ws, const FkSlice& sl, const FkProducts& prd,
+                          const std::vector<int>& rgrp, const std::vector<int>& prow) {
+  FkAltTables t{prd, {}, {}, {}, {}};
+  for (int gq = 0; gq < 9; ++gq) {
+    int cnt = 0;
+    for (int i = 0; i < prd.cnt[gq]; ++i)
+      if (rgrp[prd.off[gq] + i] < sl.n_ag) ++cnt;
+    t.pa.cnt[gq] = cnt;
+    t.pa.lay[gq] = prd.cnt[gq];
+    for (int sb = 0; prd.cnt[gq] > 0 && sb < kFkSlabs; ++sb) {
+      t.md.g[t.md.n] = gq;
+      t.md.s[t.md.n] = sb;
+      t.md.off[t.md.n] = prd.off[gq];
+      t.md.cnt[t.md.n] = cnt;
+      ++t.md.n;
+    }
+  }
+  t.md.nw = (int)sl.nw_pre;
+  for (size_t i = 0; i < sl.nw_pre; ++i) {
+    const FkWin& w = ws[sl.i0 + i];
+    t.winfo.push_back(w.blk);
+    t.winfo.push_back(w.off6);
+    if (pl.v_is_alt(w.w)) {
+      t.aperm.push_back(w.w);
+      t.aprow.insert(t.aprow.end(), prow.begin() + (long long)i * kFkParts, prow.begin() + (long long)(i + 1) * kFkParts);
+    }
+  }
+  return t;
+}
+
+// FC stage of a chunk, FC1 as the block Karatsuba: the conv6 blocks' D1 / D2 / DD, then slices of
+// whole window groups (<= fk_cap windows, SegPlan::fk_slice) in group order: window starts and output
+// rows (seg_a_rows), the slice's product and partial-row tables (host, staged), one grouped FC1
+// launch, FC2.  Segment pairs: the groups holding alt windows come first in the first slice; right
+// after it, the alt FC1 runs IN PLACE over that slice's partial rows -- the alt blocks' sequences
+// (Q), only the (product, slab, tail) partials the SNV's changed conv6 rows reach (masks per
+// M tile), the ref partials for the rest -- and the alt windows' rows are reduced and FC2'd.
+int seg_fc_karatsuba(const SegCall& c, const SegChunk& ck) {
+  expecto_beluga* h = c.h;
+  const SegPlan& pl = c.pl;
+  const hipStream_t st = c.st;
+  const int T6 = pl.g.T6, n_ph = pl.n_ph;
+  const long long nb = ck.nb, cap = pl.fk_cap;
+  const std::vector<FkWin>& ws = pl.fk_ref[ck.ci];
+  const int* perm = h->fc_perm_d + ck.w0;
+  int rc;
+  const std::vector<int> gres = pl.fk_gres(ck.ci);
+  EXPECTO_REQUIRE(nb <= kGresPerBatch * (long long)h->max_batch, "conv6 blocks of a chunk exceed fk_gres");
+  if ((rc = stage_copies(h, {{h->fk_gres, gres.data(), gres.size() * sizeof(int)}}, st)) || (rc = fk_tables(h)) ||
+      (rc = fk_seg_buffers(h)) || (rc = fk_sequences(h, h->P, nb, T6, T6, nullptr, n_ph, st, h->fk_gres)))
+    return rc;
+  bool alt_ready = false;   // alt conv6 blocks (Q) and their sequences formed (once per chunk)
+  FkSlice sl{};
+  for (size_t i0 = 0; i0 < ws.size(); i0 = sl.i1) {
+    const char* refusal = pl.fk_slice(ck.ci, i0, sl);
+    EXPECTO_REQUIRE(!refusal, refusal);
+    const int fn = (int)(sl.i1 - i0);
+    std::vector<long long> grows;
+    std::vector<int> prow, rgrp, ginfo;
+    FkProducts prd{h->fk_grows, {}, {}, {}};
+    fk_slice_tables(ws, (int)i0, (int)sl.i1, T6, grows, prd, prow, &rgrp, &ginfo);
+    if ((rc = stage_copies(h, {{h->fk_grows, grows.data(), grows.size() * sizeof(long long)},
+                               {h->fk_prow, prow.data(), prow.size() * sizeof(int)}}, st)) ||
+        (rc = seg_rows(c, ck, perm + i0, 0, fn, h->fk_arows, h->fk_crows)) ||
+        (rc = fk_fc1(h, h->P, h->fk_seq, prd, h->fk_arows, fn, h->fk_prow, h->fk_h1, st, nullptr, 0, h->fk_part,
+                     kFkParts * cap)) ||
+        (rc = seg_fc2(c, h->fk_h1, fn, c.y, h->fk_crows)))
+      return rc;
+    if (sl.n_ag == 0) continue;
+    const FkAltTables t = fk_alt_tables(pl, ws, sl, prd, rgrp, prow);
+    const int na = (int)t.aperm.size();
+    const int tiles = (int)(cap / 256 + 1);
+    if ((rc = stage_copies(h, {{h->fk_rgrp, rgrp.data(), rgrp.size() * sizeof(int)},
+                               {h->fk_ginfo, ginfo.data(), ginfo.size() * sizeof(int)},
+                               {h->fk_winfo, t.winfo.data(), t.winfo.size() * sizeof(int)},
+                               {h->fk_aperm, t.aperm.data(), t.aperm.size() * sizeof(int)},
+                               {h->fk_aprow, t.aprow.data(), t.aprow.size() * sizeof(int)}}, st)))
+      return rc;
+    if (!alt_ready) {
+      if ((rc = seg_alt_conv6(c, ck))) return rc;
+      DeltaScope ds(h);
+      if ((rc = fk_sequences(h, h->Q, nb, T6, T6, h->seg_tab, n_ph, st, h->fk_gres, 1))) return rc;
+      alt_ready = true;
+    }
+    EXPECTO_HIP_CHECK(hipMemsetAsync(h->fk_smask, 0, (size_t)(t.md.n + 1) * tiles * sizeof(unsigned), st));
+    int rows_max = t.md.nw;
+    for (int i = 0; i < t.md.n; ++i) rows_max = std::max(rows_max, t.md.cnt[i]);
+    if (rows_max > 0) {
+      fk_seg_mask<<<dim3((rows_max + 255) / 256, t.md.n + 1), dim3(256), 0, st>>>(
+          t.md, h->fk_rgrp, h->fk_ginfo, h->fk_winfo, h->seg_tab, n_ph, make_int4(0, 0, 0, 0), tiles, h->fk_smask);
+      if ((rc = check_launch("fk_seg_mask"))) return rc;
+    }
+    DeltaScope ds(h);
+    if ((rc = fk_fc1(h, h->Q, h->fk_aseq, t.pa, h->fk_arows, (int)sl.nw_pre, nullptr, h->fk_h1, st, h->fk_smask, tiles,
+                     h->fk_part, kFkParts * cap)) ||
+        (na > 0 && ((rc = fk_reduce(h, h->fk_part, h->fk_aprow, na, h->fk_h1, st)) ||
+                    (rc = seg_rows(c, ck, h->fk_aperm, 0, na, h->fk_arows, h->fk_crows)) ||
+                    (rc = seg_fc2(c, h->fk_h1, na, c.pr->y_alt, h->fk_crows)))))
+      return rc;
+  }
+  return seg_copy_tail(c, ck);
+}
+
+// FC stage of a chunk with the direct FC1: slices of <= max_batch rows (the FC1 workspace); the alt
+// FC of a slice's alt rows reuses that slice's ref partials, so it runs right after the slice's ref
+// FC1.  FC2 unsplit: the slices' h1 rows (and FC2 output rows) gather into one FC2 launch of up to
+// fc2_rows rows (split FC2: per slice)
+int seg_fc_direct(const SegCall& c, const SegChunk& ck) {
+  expecto_beluga* h = c.h;
+  const SegPairs* pr = c.pr;
+  const SegPlan& pl = c.pl;
+  const hipStream_t st = c.st;
+  const int w0 = ck.w0, nw = ck.nw;
+  int rc;
+  const int* widx = pr ? h->fc_perm_d + w0 : nullptr;   // FC row order
+  // windows of this chunk holding the SNV (alt FC: the first n_alt FC rows, widx order); the others
+  // are copies of the ref rows (seg_copy_tail)
+  const int n_alt = !pr ? 0 : (int)(std::lower_bound(pl.alt_w.begin(), pl.alt_w.end(), w0 + nw) -
+                                    std::lower_bound(pl.alt_w.begin(), pl.alt_w.end(), w0));
+  const bool gather2 = h->fc2_splits == 1;
+  int pend = 0;   // gathered h1 rows awaiting FC2
+  auto flush2 = [&]() -> int {
+    const int n2 = pend;
+    pend = 0;
+    return n2 ? run_fc2(h, h->h1, n2, c.y, st, h->c_rows) : EXPECTO_OK;
+  };
+  for (int f0 = 0; f0 < nw; f0 += h->max_batch) {
+    const int fn = std::min(h->max_batch, nw - f0);
+    if (gather2 && pend + fn > h->fc2_rows && (rc = flush2())) return rc;
+    long long* crow = h->c_rows + (gather2 ? pend : 0);
+    if ((rc = seg_rows(c, ck, widx ? widx + f0 : nullptr, w0 + f0, fn, h->a_rows, crow))) return rc;
+    if (gather2) {
+      if ((rc = run_fc1(h, h->P, h->a_rows, fn, h1_rows(h, pend), st))) return rc;
+      pend += fn;
+    } else if ((rc = run_fc(h, h->P, h->a_rows, fn, c.y, st, h->c_rows))) {
+      return rc;
+    }
+    const int na = std::min(n_alt - f0, fn);   // alt rows of this slice: [f0, f0 + na)
+    if (na <= 0) continue;
+    if (f0 == 0 && (rc = seg_alt_conv6(c, ck))) return rc;
+    long long* acrow = gather2 ? h->c_rows + h->fc2_rows : h->c_rows;   // alt rows apart
+    if ((rc = seg_rows(c, ck, widx + f0, 0, na, h->a_rows, acrow))) return rc;
+    const unsigned* mask = nullptr;
+    double frac = 1.0;
+    if (planes_gemm()) {
+      const int tiles = (int)((na + gemm_bm() - 1) / gemm_bm());
+      unsigned* md = reinterpret_cast<unsigned*>(h->slab_mask);
+      EXPECTO_HIP_CHECK(hipMemsetAsync(md, 0, tiles * sizeof(unsigned), st));
+      fc1_slab_mask_seg<<<dim3((na + 255) / 256), dim3(256), 0, st>>>(
+          widx + f0, na, h->win_seg_d, h->win_off_d, ck.s0, pl.ss, pl.g.L, c.phi, h->seg_tab, (int)gemm_bm(),
+          kFc1In / h->fc_splits, md);
+      if ((rc = check_launch("fc1_slab_mask_seg"))) return rc;
+      mask = md;
+      if (h->profiling) {   // executed share of the slabs, counted on the device (no sync)
+        if ((rc = count_slab_macs(h, md, tiles, na, st))) return rc;
+        frac = 0.0;
+      }
+    }
+    DeltaScope ds(h);
+    if (gather2) {
+      float* h1a = h1_rows(h, h->fc2_rows);
+      if ((rc = run_fc1(h, h->Q, h->a_rows, na, h1a, st, mask, frac, fn)) ||
+          (rc = run_fc2(h, h1a, na, pr->y_alt, st, acrow)))
+        return rc;
+    } else if ((rc = run_fc(h, h->Q, h->a_rows, na, pr->y_alt, st, h->c_rows, mask, frac, fn))) {
+      return rc;
+    }
+  }
+  if ((rc = flush2())) return rc;   // the ref rows are read by copy_rows below
+  return seg_copy_tail(c, ck);
+}
+
+// A segment call: the plan (seg_plan.h), the handle's per-call tables grown and staged, then per
+// chunk the trunk, its FC stage and the join of the alt runs.
 int forward_segments(expecto_beluga* h, const uint8_t* codes, int n_seg, int L, long long code_stride, int mode,
                      const int* win_seg, const int* win_off, const int* win_row, int n_win, float* y,
                      hipStream_t st, const SegPairs* pr = nullptr) {
-  EXPECTO_REQUIRE(L >= kLen && L % 4 == 0, "segment length must be >= 2000 and a multiple of 4");
   g_precision = h->precision;
   g_conv_ea = h->conv_ea;
+  SegPlan pl;
+  const char* refusal = nullptr;
+  if (seg_plan({n_seg, L, mode, win_seg, win_off, win_row, n_win, pr ? pr->var_pos : nullptr,
+                pr ? pr->strand_stride : n_win, h->max_batch, p_floats(h->max_batch) - 16 * 640,
+                q_floats(h->max_batch) - 16 * 640, h->seg_merge_strands, h->seg_chunk_windows, fk_use_seg(h), fk_cap(h)},
+               pl, &refusal)) {
+    set_error(refusal);
+    return EXPECTO_EINVAL;
+  }
   int rc;
   if (pr && (rc = ensure_delta(h))) return rc;
-  // phases present (fwd and, for BOTH, the mirrored rc offsets)
-  int present[4] = {0, 0, 0, 0};
-  for (int w = 0; w < n_win; ++w) {
-    EXPECTO_REQUIRE(win_seg[w] >= 0 && win_seg[w] < n_seg, "window segment out of range");
-    EXPECTO_REQUIRE(w == 0 || win_seg[w] >= win_seg[w - 1], "windows must be sorted by segment");
-    const int o = win_off[w];
-    EXPECTO_REQUIRE(o >= 0 && o % 4 == 0 && o + kLen <= L, "window offset must be 4-aligned inside the segment");
-    // phases in the computed strands' coordinates (seg_a_rows: rc windows start at L - 2000 - o)
-    if (mode != EXPECTO_STRAND_RC) present[(o >> 2) & 3] = 1;
-    if (mode != EXPECTO_STRAND_FWD) present[((L - kLen - o) >> 2) & 3] = 1;
-  }
-  int n_ph = 0, ph[4] = {0, 0, 0, 0}, ph_idx[4] = {0, 0, 0, 0};
-  for (int p = 0; p < 4; ++p)
-    if (present[p]) {
-      ph_idx[p] = n_ph;
-      ph[n_ph++] = p;
-    }
-  const SegGeo g = seg_geo(L, std::max(n_ph, 1));
-  const size_t p_cap = p_floats(h->max_batch) - 16 * 640, q_cap = q_floats(h->max_batch) - 16 * 640;
-  const int seg_cap = (int)std::min<size_t>(p_cap / g.p_rows_floats, q_cap / g.q_rows_floats);
-  EXPECTO_REQUIRE(seg_cap >= 1, "segment too long for this handle's workspace (raise max_batch)");
-  // window ranges per segment
-  std::vector<int> first(n_seg + 1, n_win);
-  for (int w = n_win - 1; w >= 0; --w) first[win_seg[w]] = w;
-  for (int sg = n_seg - 1; sg >= 0; --sg) first[sg] = std::min(first[sg], first[sg + 1]);
   if (n_win > h->win_cap) {
     for (int** b : {&h->win_seg_d, &h->win_off_d, &h->win_row_d, &h->alt_w_d, &h->copy_w_d, &h->fc_perm_d}) {
       if (*b) EXPECTO_HIP_CHECK(hipFree(*b));
@@ -2943,533 +3278,37 @@ int forward_segments(expecto_beluga* h, const uint8_t* codes, int n_seg, int L, 
     EXPECTO_HIP_CHECK(hipMalloc(&h->fc_perm_d, 4 * n_win * sizeof(int)));   // per strand: FC order, alt order
     h->win_cap = n_win;
   }
-  // (strand, segment) entries and their windows, the fwd strand's first (SegStrands)
-  const int strands = mode == EXPECTO_STRAND_BOTH ? 2 : 1;
-  const int n_ent = strands * n_seg, n_vw = strands * n_win;
-  const SegStrands ss{n_seg, mode == EXPECTO_STRAND_FWD ? n_ent : mode == EXPECTO_STRAND_RC ? 0 : n_seg,
-                      n_win, mode == EXPECTO_STRAND_FWD ? n_vw : mode == EXPECTO_STRAND_RC ? 0 : n_win,
-                      pr ? pr->strand_stride : n_win};
-  auto vw_w = [&](int v) { return v >= n_win ? v - n_win : v; };
-  std::vector<int> vfirst(n_ent + 1, n_vw);   // first window of entry e
-  for (int e = 0; e < n_ent; ++e) vfirst[e] = e >= n_seg ? n_win + first[e - n_seg] : first[e];
-  std::vector<char> is_alt(n_win, 0);
-  std::vector<int> alt_w, copy_w;   // window numbers, ascending
-  if (pr) {
-    for (int sg = 0; sg < n_seg; ++sg)
-      EXPECTO_REQUIRE(pr->var_pos[sg] >= 0 && pr->var_pos[sg] < L, "variant position outside its segment");
-    for (int w = 0; w < n_win; ++w) {
-      const int q = pr->var_pos[win_seg[w]];
-      is_alt[w] = win_off[w] <= q && q < win_off[w] + kLen;
-    }
-    for (int v = 0; v < n_vw; ++v) (is_alt[vw_w(v)] ? alt_w : copy_w).push_back(v);
-    if (n_seg > h->seg_var_cap) {
-      if (h->seg_var_d) EXPECTO_HIP_CHECK(hipFree(h->seg_var_d));
-      h->seg_var_d = nullptr;
-      h->seg_var_cap = 0;
-      EXPECTO_HIP_CHECK(hipMalloc(&h->seg_var_d, n_seg * sizeof(int)));
-      h->seg_var_cap = n_seg;
-    }
-  }
-  std::vector<HostCopy> copies;   // staged once the FC row order is known (below)
-  if (pr) {
-    copies.push_back({h->seg_var_d, pr->var_pos, n_seg * sizeof(int)});
-    copies.push_back({h->alt_w_d, alt_w.data(), alt_w.size() * sizeof(int)});
-    copies.push_back({h->copy_w_d, copy_w.data(), copy_w.size() * sizeof(int)});
-  }
-  if (win_row) {
-    for (int w = 0; w < n_win; ++w) EXPECTO_REQUIRE(win_row[w] >= 0 && win_row[w] < n_win, "window row out of range");
-    copies.push_back({h->win_row_d, win_row, n_win * sizeof(int)});
-  }
-  copies.push_back({h->win_seg_d, win_seg, n_win * sizeof(int)});
-  copies.push_back({h->win_off_d, win_off, n_win * sizeof(int)});
-  // alt runs: one block per segment (conv1..4) or per (segment, phase) (pool2, conv5, conv6)
-  const int blk_per_seg = pr ? std::max(n_ph, 1) : 0;
-  // chunks of whole (strand, segment) entries: grow while the segment buffers and the alt-run
-  // buffers (<= max_batch blocks) fit.  The FC stage of a chunk runs in slices of <= max_batch
-  // windows (its workspace), so a chunk is not bounded by its window count: one large chunk instead
-  // of several keeps every conv launch's last partial round of 256 workgroups to one per chunk (the
-  // 200-window workload: 96 segments per strand in one chunk instead of 40 + 40 + 16), and a chunk
-  // runs on across the strand boundary (both strands' 192 entries in one chunk: every stage is
-  // launched once per step, not once per strand; EXPECTO_SEG_MERGE_STRANDS=0 ends a chunk there)
-  std::vector<std::pair<int, int>> chunks;
-  for (int e0 = 0; e0 < n_ent;) {
-    int e1 = e0 + 1;
-    while (e1 < n_ent && (e1 != n_seg || h->seg_merge_strands) && e1 - e0 < seg_cap &&
-           (long long)(e1 + 1 - e0) * blk_per_seg <= h->max_batch &&
-           (h->seg_chunk_windows <= 0 || vfirst[e1 + 1] - vfirst[e0] <= h->seg_chunk_windows))
-      ++e1;
-    chunks.push_back({e0, e1});
-    e0 = e1;
-  }
-  // Segment pairs: the FC rows of a chunk are its alt windows sorted by the SNV's position in
-  // the window (in the window's strand orientation), then the other windows.  The ref FC1 runs in
-  // that order, and the alt FC1 over the first rows recomputes only the split-K slabs its changed
-  // conv6 rows touch (a 256-row tile then holds windows with nearly the same changed rows), reusing
-  // the ref partials.
-  std::vector<int> fc_perm;
-  if (pr) {
-    fc_perm.resize((size_t)n_vw);
-    auto pos_of = [&](int v) {
-      const int w = vw_w(v), p = pr->var_pos[win_seg[w]] - win_off[w];
-      return v >= ss.rc_win ? kLen - 1 - p : p;
-    };
-    for (const auto& c : chunks) {
-      const int w0 = vfirst[c.first], w1 = vfirst[c.second];
-      int k = w0;
-      std::vector<int> a;
-      for (int v = w0; v < w1; ++v)
-        if (is_alt[vw_w(v)]) a.push_back(v);
-      std::stable_sort(a.begin(), a.end(), [&](int x, int y) { return pos_of(x) < pos_of(y); });
-      for (int v : a) fc_perm[k++] = v;
-      for (int v = w0; v < w1; ++v)
-        if (!is_alt[vw_w(v)]) fc_perm[k++] = v;
-    }
-    copies.push_back({h->fc_perm_d, fc_perm.data(), fc_perm.size() * sizeof(int)});
-  }
-  // FC1 as the block Karatsuba (f16x3): per strand and chunk the windows in group order (conv6
-  // block, group start, role), the FC order of every launch and (segment pairs) the alt windows in
-  // the same order; fc_perm_d holds [strand][n_win] FC orders, then [strand][n_win] alt orders
-  // Segment pairs where more than a third of the windows hold the SNV (short sweeps: +-800, every
-  // window) run the direct FC1 (role 4): an alt window's Karatsuba products mix rows 25-75 apart, so
-  // nearly all of them reach the changed rows and the alt recompute outweighs the saving
-  // (configs[2]: 14.4 k vs 16.6 k variants/s); the 200-window sweeps (5 % alt windows) gain.
-  const bool fkm = fk_use_seg(h) && !(pr && 3 * alt_w.size() > (size_t)n_vw);
-  std::vector<std::vector<FkWin>> fk_ref, fk_alt;   // [chunk]
-  auto fk_is_alt = [&](int v) { return is_alt[vw_w(v)] != 0; };
-  if (fkm) {
-    fc_perm.assign((size_t)4 * n_win, 0);
-    for (const auto& c : chunks) {
-      const int w0 = vfirst[c.first], w1 = vfirst[c.second];
-      // group order: (segment pairs) the groups holding an alt window first, ordered by where the
-      // SNV falls in the group (so an M tile of the in-place alt FC1 holds groups whose changed
-      // products are the same and its masks stay sparse), then every other group; in a group its
-      // windows by role
-      struct Key {
-        int cls;
-        long long rel;
-        int blk, G, off6, w;
-      };
-      std::vector<FkWin> ref, alt;
-      std::vector<Key> key;
-      std::map<std::pair<int, int>, int> galt;   // (block, group start) -> holds an alt window
-      for (int v = w0; v < w1; ++v) {   // a group lies in one block, so it never mixes strands
-        const int w = vw_w(v);
-        const FkWin fw = fk_win(v, win_seg[w] + (v >= n_win ? n_seg : 0) - c.first, win_off[w], v >= ss.rc_win, L, n_ph,
-                                ph_idx);
-        ref.push_back(fw);
-        if (pr && fk_is_alt(v)) {
-          alt.push_back(fw);
-          galt[{fw.blk, fw.off6 - 25 * fk_role_of(fw.off6)}] = 1;
-        }
-      }
-      for (const FkWin& fw : ref) {
-        const int G = fw.off6 - 25 * fk_role_of(fw.off6);
-        const bool ga = pr && galt.count({fw.blk, G});
-        long long rel = 0;
-        if (ga) {
-          const int q = pr->var_pos[win_seg[vw_w(fw.w)]];
-          rel = (long long)(fw.w >= ss.rc_win ? L - 1 - q : q) - 16LL * G;
-        }
-        key.push_back({ga ? 0 : 1, rel, fw.blk, G, fw.off6, fw.w});
-      }
-      std::vector<int> ord(ref.size());
-      for (size_t k = 0; k < ord.size(); ++k) ord[k] = (int)k;
-      std::sort(ord.begin(), ord.end(), [&](int a, int b) {
-        const Key &x = key[a], &y = key[b];
-        return std::tie(x.cls, x.rel, x.blk, x.G, x.off6, x.w) < std::tie(y.cls, y.rel, y.blk, y.G, y.off6, y.w);
-      });
-      std::vector<FkWin> sorted;
-      for (int k : ord) sorted.push_back(ref[k]);
-      for (size_t k = 0; k < sorted.size(); ++k) fc_perm[(size_t)w0 + k] = sorted[k].w;
-      fk_ref.push_back(std::move(sorted));
-      fk_alt.push_back(std::move(alt));
-    }
-    if (pr) copies.pop_back();   // the pair order above is replaced by the group order
-    copies.push_back({h->fc_perm_d, fc_perm.data(), fc_perm.size() * sizeof(int)});
+  if (pr && n_seg > h->seg_var_cap) {
+    if (h->seg_var_d) EXPECTO_HIP_CHECK(hipFree(h->seg_var_d));
+    h->seg_var_d = nullptr;
+    h->seg_var_cap = 0;
+    EXPECTO_HIP_CHECK(hipMalloc(&h->seg_var_d, n_seg * sizeof(int)));
+    h->seg_var_cap = n_seg;
   }
   // the tables are caller-owned (and local) host memory: stage them through pinned memory
+  std::vector<HostCopy> copies;
+  if (pr) {
+    copies.push_back({h->seg_var_d, pr->var_pos, n_seg * sizeof(int)});
+    copies.push_back({h->alt_w_d, pl.alt_w.data(), pl.alt_w.size() * sizeof(int)});
+    copies.push_back({h->copy_w_d, pl.copy_w.data(), pl.copy_w.size() * sizeof(int)});
+  }
+  if (win_row) copies.push_back({h->win_row_d, win_row, n_win * sizeof(int)});
+  copies.push_back({h->win_seg_d, win_seg, n_win * sizeof(int)});
+  copies.push_back({h->win_off_d, win_off, n_win * sizeof(int)});
+  if (!pl.fc_perm.empty()) copies.push_back({h->fc_perm_d, pl.fc_perm.data(), pl.fc_perm.size() * sizeof(int)});
   if ((rc = stage_copies(h, copies, st))) return rc;
-  const int eb = act_bytes();
-  hipStream_t sa = (pr && h->st2) ? h->st2 : st;     // alt runs of segment pairs
-  const SegDims gd{L, g.T1, g.P1, g.T3, g.T4, g.S5, g.T5, g.T6};
-  const int4 ph4 = make_int4(ph[0], ph[1], ph[2], ph[3]);
-  for (const auto& chunk : chunks) {
-    const int s0 = chunk.first, s1 = chunk.second;   // entries [s0, s1), windows [w0, w0 + nw)
-    const int w0 = vfirst[s0], nw = vfirst[s1] - vfirst[s0];
-    const int ns = s1 - s0;
-    const long long nb = (long long)ns * n_ph;
-    // Alt runs (segment pairs) on the handle's second stream `sa`: the alt input patch of
-    // layer l is assembled from the ref input of layer l (`ref`, ref_rows per block; the
-    // ref layer l reads it concurrently) and the previous alt run, then the layer's GEMM runs
-    // on it beside the next ref layers.  The ref launch that next overwrites `ref` (ping-
-    // pong) waits for the assembly (event `done`).  Same kernels, K order and weights.
-    auto alt_asm = [&](int l, const float* ref, int ref_rows, const float* dprev, int wprev, int nbk, int ib,
-                       int mult, int irp, int arows, hipEvent_t ready, hipEvent_t done) -> int {
-      if (sa != st) {
-        EXPECTO_HIP_CHECK(hipEventRecord(ready, st));
-        EXPECTO_HIP_CHECK(hipStreamWaitEvent(sa, ready, 0));
-      }
-      const int row16 = kConv[l].cin * eb / 16;
-      seg_delta_assemble<<<dim3(ns * nbk), dim3(256), 0, sa>>>(ref, ref_rows, dprev, wprev, h->seg_tab, nbk,
-                                                                    ib, mult, irp, arows, row16, h->DA);
-      int r = check_launch("seg_delta_assemble");
-      if (!r && sa != st) EXPECTO_HIP_CHECK(hipEventRecord(done, sa));
-      return r;
-    };
-    auto alt_gemm = [&](int l, int nbk, int arows, int w, bool pool, float* dnext) -> int {
-      DeltaScope ds(h);
-      return run_conv(h, l, h->DA, dnext, (long long)ns * nbk, arows, w, w, pool, sa);
-    };
-    auto st_wait = [&](hipEvent_t e) -> int {   // st: the alt work recorded in e is done
-      if (sa != st) EXPECTO_HIP_CHECK(hipStreamWaitEvent(st, e, 0));
-      return EXPECTO_OK;
-    };
-    if (pr && sa != st) {   // sa: the previous chunk's use of the alt buffers on st is done
-      EXPECTO_HIP_CHECK(hipEventRecord(h->pev[0], st));
-      EXPECTO_HIP_CHECK(hipStreamWaitEvent(sa, h->pev[0], 0));
-    }
-    // conv1 from codes: virtual rows = the chunk's entries, code rows s0.. of the call's n_seg in
-    // its strand mode (BOTH: rows >= n_seg are the rc strand's); the kernel mirrors the rc rows
-    // (fused: inside the conv2 launch)
-    const bool kmer = use_kmer(h, nullptr);
-    const bool fuse = !kmer && fuse_conv1(h, nullptr);
-    const C1Src f1{codes, code_stride, n_seg, mode, s0, L};
-    if (!kmer && !fuse && (rc = run_conv1(h, nullptr, codes, code_stride, n_seg, mode, s0, ns, L, g.S1, st)))
-      return rc;
-    if (pr) {
-      seg_delta_table<<<dim3((ns + 255) / 256), dim3(256), 0, sa>>>(h->seg_var_d, s0, ns, ss, gd, n_ph, ph4,
-                                                                   h->seg_tab);
-      if ((rc = check_launch("seg_delta_table"))) return rc;
-      if (kmer || fuse) {   // the alt conv2 patch straight from the alt codes (k-mer table, or conv1 -> DA)
-        seg_delta_codes2<<<dim3((ns + 4) / 5), dim3(5 * kC1PatStride), 0, sa>>>(
-            codes, code_stride, pr->alt_code, s0, ns, ss, L, h->seg_tab, h->delta_codes);
-        if ((rc = check_launch("seg_delta_codes2"))) return rc;
-        DeltaScope ds(h);
-        if (fuse && (rc = run_conv1(h, nullptr, h->delta_codes, kC1PatStride, ns, EXPECTO_STRAND_FWD, 0, ns, kC1Pat,
-                                    kDA[2], sa, h->DA)))
-          return rc;
-      } else {
-        seg_delta_codes<<<dim3((ns + 15) / 16), dim3(256), 0, sa>>>(codes, code_stride, pr->alt_code, s0, ns, ss,
-                                                                   L, h->seg_tab, h->delta_codes);
-        if ((rc = check_launch("seg_delta_codes"))) return rc;
-        DeltaScope ds(h);
-        if ((rc = run_conv1(h, nullptr, h->delta_codes, 16, ns, EXPECTO_STRAND_FWD, 0, ns, kDA[1], kDW[1], sa,
-                            h->D0)))
-          return rc;
-      }
-    }
-    // conv2 + pool1 (P -> Q), conv3 (Q -> P), conv4 unpooled (P -> Q); alt runs D0 <-> D1
-    if (pr && !kmer && !fuse && (rc = alt_asm(0, h->P, g.S1, h->D0, kDW[1], 1, 2, 4, 1, kDA[2], h->pev[1], h->pev[2])))
-      return rc;
-    if (kmer)
-      rc = run_conv2_kmer(h, f1, ns, g.P1, g.P1, h->Q, st);
-    else
-      rc = run_conv(h, 0, h->P, h->Q, ns, g.S1, g.P1, g.P1, true, st, fuse ? &f1 : nullptr);
-    if (rc) return rc;
-    if (pr && kmer) {   // alt pooled conv2 rows [r2, r2 + kDW[2]) of each segment into D1
-      DeltaScope ds(h);
-      const C1Src fa{h->delta_codes, kC1PatStride, ns, EXPECTO_STRAND_FWD, 0, kC1Pat};
-      if ((rc = run_conv2_kmer(h, fa, ns, kDW[2], kDW[2], h->D1, sa))) return rc;
-    } else if (pr && ((!fuse && (rc = st_wait(h->pev[2]))) || (rc = alt_gemm(0, 1, kDA[2], kDW[2], true, h->D1)))) {
-      return rc;
-    }
-    if (pr && (rc = alt_asm(1, h->Q, g.P1, h->D1, kDW[2], 1, 3, 1, 2, kDA[3], h->pev[3], h->pev[4]))) return rc;
-    // conv3 rows at a 4-aligned stride per segment (T3p >= T3), so conv4's rows of every segment
-    // start 4-aligned in its M index space: pool2 groups are then lane-local (epilogue_pool_ph02)
-    const int T3p = (g.T3 + 3) & ~3;
-    if ((rc = run_conv(h, 1, h->Q, h->P, ns, g.P1, g.T3, T3p, false, st))) return rc;
-    if (pr && ((rc = st_wait(h->pev[4])) || (rc = alt_gemm(1, 1, kDA[3], kDW[3], false, h->D0)))) return rc;
-    if (pr && (rc = alt_asm(2, h->P, T3p, h->D0, kDW[3], 1, 4, 1, 3, kA4u, h->pev[5], h->pev[6]))) return rc;
-    // pool2 fused into conv4 (P -> phase blocks in Q, then P and Q trade roles for the rest of
-    // the chunk: conv5 Q -> P, conv6 P -> Q, ... -- both hold a chunk's conv5 / conv6 rows, see
-    // seg_geo), else conv4 unpooled (P -> Q) and a pool pass (Q -> P)
-    const bool pfused = conv4_pool_fused(h, (long long)ns * T3p, n_ph, ph);
-    struct PQSwap {
-      expecto_beluga* h;
-      bool on;
-      ~PQSwap() {
-        if (on) std::swap(h->P, h->Q);
-      }
-    } pq{h, false};
-    if (pfused) {
-      if ((rc = run_conv4_pool_fused(h, h->P, h->Q, ns, T3p, g.T4, g.S5, pr ? h->seg_tab : nullptr, st))) return rc;
-      std::swap(h->P, h->Q);
-      pq.on = true;
-    } else if ((rc = run_conv(h, 2, h->P, h->Q, ns, T3p, g.T4, g.T4, false, st))) {
-      return rc;
-    }
-    if (pr && ((rc = st_wait(h->pev[6])) || (rc = alt_gemm(2, 1, kA4u, kW4u, false, h->D1)))) return rc;
-    if (!pfused) {  // pool2 phases (Q -> P)
-      LayerTimer lt(h, 3, st);
-      if (act_fmt() == 2 && h->pool_one_pass) {   // all phases in one pass over the conv4 rows
-        dim3 grid((g.S5 + 3) / 4, ns);
-        pool4_phases_h2m<<<grid, dim3(256), 0, st>>>(h->Q, g.T4, g.T4, 480, n_ph, ph4, g.S5, h->P);
-      } else if (act_fmt() == 2) {
-        dim3 grid((g.S5 + 3) / 4, ns * n_ph);
-        pool4_phases_h2<<<grid, dim3(256), 0, st>>>(h->Q, g.T4, g.T4, 480, n_ph, ph4, g.S5, h->P);
-      } else {
-        dim3 grid(g.S5, ns * n_ph);
-        pool4_phases<<<grid, dim3(480), 0, st>>>(h->Q, ns, g.T4, g.T4, 480, n_ph, ph4, g.S5, h->P, act_fmt());
-      }
-      if ((rc = check_launch("pool4_phases"))) return rc;
-    }
-    if (pr) {   // alt pool2 phases from the unpooled conv4 rows (Q) and the alt conv4 run
-      if (sa != st) {
-        EXPECTO_HIP_CHECK(hipEventRecord(h->pev[7], st));
-        EXPECTO_HIP_CHECK(hipStreamWaitEvent(sa, h->pev[7], 0));
-      }
-      seg_delta_pool<<<dim3(kDW[4], (unsigned)nb), dim3(480), 0, sa>>>(pfused ? h->edge : h->Q, g.T4, h->D1, n_ph,
-                                                                       ph4, h->seg_tab, act_fmt(), h->D0,
-                                                                       pfused ? 1 : 0);
-      if ((rc = check_launch("seg_delta_pool"))) return rc;
-      if (sa != st) EXPECTO_HIP_CHECK(hipEventRecord(h->pev[8], sa));
-      if ((rc = alt_asm(3, h->P, g.S5, h->D0, kDW[4], n_ph, 9, 1, 5, kDA[5], h->pev[9], h->pev[10]))) return rc;
-      if ((rc = st_wait(h->pev[8]))) return rc;    // conv5 overwrites Q
-    }
-    // conv5 (P -> Q), conv6 (Q -> P) over (segment, phase) blocks
-    if ((rc = run_conv(h, 3, h->P, h->Q, nb, g.S5, g.T5, g.T5, false, st))) return rc;
-    if (pr && ((rc = st_wait(h->pev[10])) || (rc = alt_gemm(3, n_ph, kDA[5], kDW[5], false, h->D1)))) return rc;
-    if (pr && (rc = alt_asm(4, h->Q, g.T5, h->D1, kDW[5], n_ph, 13, 1, 9, kDA[6], h->pev[11], h->pev[12])))
-      return rc;
-    if ((rc = run_conv(h, 4, h->Q, h->P, nb, g.T5, g.T6, g.T6, false, st))) return rc;
-    if (pr) {
-      if ((rc = alt_gemm(4, n_ph, kDA[6], kDW[6], false, h->D0))) return rc;
-      if (sa != st) EXPECTO_HIP_CHECK(hipEventRecord(h->pev[13], sa));   // all alt runs of the chunk
-    }
-    if (nw > 0 && fkm) {
-      // FC1 as the block Karatsuba: the conv6 blocks' D1 / D2 / DD, then slices of whole window
-      // groups (<= fk_cap windows) in group order: window starts and output rows (seg_a_rows),
-      // the slice's product and partial-row tables (host, staged), one grouped FC1 launch, FC2.
-      // Segment pairs: the groups holding alt windows come first in the first slice; right after
-      // it, the alt FC1 runs IN PLACE over that slice's partial rows -- the alt blocks' sequences
-      // (Q), only the (product, slab, tail) partials the SNV's changed conv6 rows reach (masks per
-      // M tile), the ref partials for the rest -- and the alt windows' rows are reduced and FC2'd.
-      const int4 phi = make_int4(ph_idx[0], ph_idx[1], ph_idx[2], ph_idx[3]);
-      const size_t ci = (size_t)(&chunk - chunks.data());
-      const long long cap = fk_cap(h);
-      const std::vector<FkWin>& ws = fk_ref[ci];
-      const int* perm = h->fc_perm_d + w0;
-      // per conv6 block: its groups' start residue mod 100 (all equal on 200-bp sweeps), so the
-      // sequences are formed only on the rows the products read; -2: a block no window reads
-      std::vector<int> gres((size_t)nb, -2);
-      for (const FkWin& w : ws) {
-        const int r = (w.off6 - 25 * fk_role_of(w.off6)) % 100;
-        int& e = gres[(size_t)w.blk];
-        e = e == -2 ? r : (e == r ? r : -1);
-      }
-      EXPECTO_REQUIRE(nb <= kGresPerBatch * (long long)h->max_batch, "conv6 blocks of a chunk exceed fk_gres");
-      if ((rc = stage_copies(h, {{h->fk_gres, gres.data(), gres.size() * sizeof(int)}}, st)) || (rc = fk_tables(h)) ||
-          (rc = fk_seg_buffers(h)) || (rc = fk_sequences(h, h->P, nb, g.T6, g.T6, nullptr, n_ph, st, h->fk_gres)))
-        return rc;
-      const bool has_alt = pr && !fk_alt[ci].empty();
-      bool alt_ready = false;   // alt conv6 blocks (Q) and their sequences formed (once per chunk)
-      for (size_t i0 = 0; i0 < ws.size();) {
-        size_t i1 = i0;
-        while (i1 < ws.size()) {   // whole groups, <= fk_cap windows
-          size_t j = i1 + 1;
-          while (j < ws.size() && fk_same_group(ws[j], ws[i1])) ++j;
-          if (j - i0 > (size_t)cap && i1 > i0) break;
-          i1 = j;
-        }
-        EXPECTO_REQUIRE(i1 - i0 <= (size_t)cap, "a Karatsuba FC1 window group exceeds the FC1 slice");
-        const int fn = (int)(i1 - i0);
-        std::vector<long long> grows;
-        std::vector<int> prow, rgrp, ginfo;
-        FkProducts prd{h->fk_grows, {}, {}, {}};
-        fk_slice_tables(ws, (int)i0, (int)i1, g.T6, grows, prd, prow, &rgrp, &ginfo);
-        if ((rc = stage_copies(h, {{h->fk_grows, grows.data(), grows.size() * sizeof(long long)},
-                                   {h->fk_prow, prow.data(), prow.size() * sizeof(int)}}, st)))
-          return rc;
-        seg_a_rows<<<dim3((fn + 255) / 256), dim3(256), 0, st>>>(
-            h->win_seg_d, h->win_off_d, win_row ? h->win_row_d : nullptr, perm + i0, 0, fn, s0, ss, L, n_ph, phi,
-            g.T6, h->fk_arows, h->fk_crows);
-        if ((rc = check_launch("seg_a_rows")) ||
-            (rc = fk_fc1(h, h->P, h->fk_seq, prd, h->fk_arows, fn, h->fk_prow, h->fk_h1, st, nullptr, 0, h->fk_part,
-                         kFkParts * cap)))
-          return rc;
-        for (int r0 = 0; r0 < fn; r0 += h->max_batch)   // FC2 over its workspace's max_batch rows at a time
-          if ((rc = run_fc2(h, h->fk_h1 + (long long)r0 * kHidLd, std::min(h->max_batch, fn - r0), y, st,
-                            h->fk_crows + r0)))
-            return rc;
-        // the slice's first groups holding alt windows (the alt groups lead the chunk's order, so
-        // they fill the first slices) and their windows
-        int n_ag = 0;
-        size_t nw_pre = 0;
-        for (size_t i = i0; has_alt && i < i1; ++i) {
-          bool galt = false;
-          size_t j = i;
-          for (; j < i1 && fk_same_group(ws[j], ws[i]); ++j) galt |= fk_is_alt(ws[j].w);
-          if (!galt) break;
-          ++n_ag;
-          nw_pre = j - i0;
-          i = j - 1;
-        }
-        if (n_ag > 0) {
-          FkProducts pa = prd;   // the alt groups' prefix of every product list, in the ref layout
-          FkMaskDesc md{};
-          for (int gq = 0; gq < 9; ++gq) {
-            int c = 0;
-            for (int i = 0; i < prd.cnt[gq]; ++i)
-              if (rgrp[prd.off[gq] + i] < n_ag) ++c;
-            pa.cnt[gq] = c;
-            pa.lay[gq] = prd.cnt[gq];
-            for (int sb = 0; prd.cnt[gq] > 0 && sb < kFkSlabs; ++sb) {
-              md.g[md.n] = gq;
-              md.s[md.n] = sb;
-              md.off[md.n] = prd.off[gq];
-              md.cnt[md.n] = c;
-              ++md.n;
-            }
-          }
-          md.nw = (int)nw_pre;
-          std::vector<int> winfo, aperm, aprow;
-          for (size_t i = 0; i < nw_pre; ++i) {
-            winfo.push_back(ws[i0 + i].blk);
-            winfo.push_back(ws[i0 + i].off6);
-            if (fk_is_alt(ws[i0 + i].w)) {
-              aperm.push_back(ws[i0 + i].w);
-              aprow.insert(aprow.end(), prow.begin() + (long long)i * kFkParts, prow.begin() + (long long)(i + 1) * kFkParts);
-            }
-          }
-          const int na = (int)aperm.size();
-          const int tiles = (int)(cap / 256 + 1);
-          if ((rc = stage_copies(h, {{h->fk_rgrp, rgrp.data(), rgrp.size() * sizeof(int)},
-                                     {h->fk_ginfo, ginfo.data(), ginfo.size() * sizeof(int)},
-                                     {h->fk_winfo, winfo.data(), winfo.size() * sizeof(int)},
-                                     {h->fk_aperm, aperm.data(), aperm.size() * sizeof(int)},
-                                     {h->fk_aprow, aprow.data(), aprow.size() * sizeof(int)}}, st)))
-            return rc;
-          if (!alt_ready) {
-            if ((rc = st_wait(h->pev[13]))) return rc;   // alt conv6 runs (and the Q reads of their patches)
-            seg_alt_blocks<<<dim3(kAltRows6, (unsigned)nb), dim3(64), 0, st>>>(h->P, h->D0, n_ph, g.T6, h->seg_tab,
-                                                                              640 * eb / 16, h->Q);
-            if ((rc = check_launch("seg_alt_blocks"))) return rc;
-            DeltaScope ds(h);
-            if ((rc = fk_sequences(h, h->Q, nb, g.T6, g.T6, h->seg_tab, n_ph, st, h->fk_gres, 1))) return rc;
-            alt_ready = true;
-          }
-          EXPECTO_HIP_CHECK(hipMemsetAsync(h->fk_smask, 0, (size_t)(md.n + 1) * tiles * sizeof(unsigned), st));
-          int rows_max = md.nw;
-          for (int i = 0; i < md.n; ++i) rows_max = std::max(rows_max, md.cnt[i]);
-          if (rows_max > 0) {
-            fk_seg_mask<<<dim3((rows_max + 255) / 256, md.n + 1), dim3(256), 0, st>>>(
-                md, h->fk_rgrp, h->fk_ginfo, h->fk_winfo, h->seg_tab, n_ph, make_int4(0, 0, 0, 0), tiles, h->fk_smask);
-            if ((rc = check_launch("fk_seg_mask"))) return rc;
-          }
-          DeltaScope ds(h);
-          if ((rc = fk_fc1(h, h->Q, h->fk_aseq, pa, h->fk_arows, (int)nw_pre, nullptr, h->fk_h1, st, h->fk_smask, tiles,
-                           h->fk_part, kFkParts * cap)) ||
-              (na > 0 && (rc = fk_reduce(h, h->fk_part, h->fk_aprow, na, h->fk_h1, st))))
-            return rc;
-          if (na > 0) {
-            seg_a_rows<<<dim3((na + 255) / 256), dim3(256), 0, st>>>(
-                h->win_seg_d, h->win_off_d, win_row ? h->win_row_d : nullptr, h->fk_aperm, 0, na, s0, ss, L, n_ph,
-                phi, g.T6, h->fk_arows, h->fk_crows);
-            if ((rc = check_launch("seg_a_rows"))) return rc;
-            for (int r0 = 0; r0 < na; r0 += h->max_batch)
-              if ((rc = run_fc2(h, h->fk_h1 + (long long)r0 * kHidLd, std::min(h->max_batch, na - r0), pr->y_alt, st,
-                                h->fk_crows + r0)))
-                return rc;
-          }
-        }
-        i0 = i1;
-      }
-      if (pr) {
-        const int ic0 = (int)(std::lower_bound(copy_w.begin(), copy_w.end(), w0) - copy_w.begin());
-        const int ic1 = (int)(std::lower_bound(copy_w.begin(), copy_w.end(), w0 + nw) - copy_w.begin());
-        if (ic1 > ic0) {
-          copy_rows<<<dim3(ic1 - ic0), dim3(256), 0, st>>>(y, pr->y_alt, h->copy_w_d + ic0,
-                                                           win_row ? h->win_row_d : nullptr, n_win, ss.rc_rows);
-          if ((rc = check_launch("copy_rows"))) return rc;
-        }
-      }
-    } else if (nw > 0) {
-      const int4 phi = make_int4(ph_idx[0], ph_idx[1], ph_idx[2], ph_idx[3]);
-      const int* widx = pr ? h->fc_perm_d + w0 : nullptr;   // FC row order
-      // windows of this chunk holding the SNV (alt FC: the first n_alt FC rows, widx order) and
-      // the others (copies of the ref rows)
-      int n_alt = 0, ic0 = 0, ic1 = 0;
-      if (pr) {
-        n_alt = (int)(std::lower_bound(alt_w.begin(), alt_w.end(), w0 + nw) -
-                      std::lower_bound(alt_w.begin(), alt_w.end(), w0));
-        ic0 = (int)(std::lower_bound(copy_w.begin(), copy_w.end(), w0) - copy_w.begin());
-        ic1 = (int)(std::lower_bound(copy_w.begin(), copy_w.end(), w0 + nw) - copy_w.begin());
-      }
-      // FC1 slices of <= max_batch rows (the FC1 workspace); the alt FC of a slice's alt rows
-      // reuses that slice's ref partials, so it runs right after the slice's ref FC1.  FC2
-      // unsplit: the slices' h1 rows (and FC2 output rows) gather into one FC2 launch of up to
-      // fc2_rows rows (split FC2: per slice)
-      const bool gather2 = h->fc2_splits == 1;
-      int pend = 0;   // gathered h1 rows awaiting FC2
-      auto flush2 = [&]() -> int {
-        const int n2 = pend;
-        pend = 0;
-        return n2 ? run_fc2(h, h->h1, n2, y, st, h->c_rows) : EXPECTO_OK;
-      };
-      for (int f0 = 0; f0 < nw; f0 += h->max_batch) {
-        const int fn = std::min(h->max_batch, nw - f0);
-        if (gather2 && pend + fn > h->fc2_rows && (rc = flush2())) return rc;
-        long long* crow = h->c_rows + (gather2 ? pend : 0);
-        seg_a_rows<<<dim3((fn + 255) / 256), dim3(256), 0, st>>>(
-            h->win_seg_d, h->win_off_d, win_row ? h->win_row_d : nullptr, widx ? widx + f0 : nullptr, w0 + f0,
-            fn, s0, ss, L, n_ph, phi, g.T6, h->a_rows, crow);
-        if ((rc = check_launch("seg_a_rows"))) return rc;
-        if (gather2) {
-          if ((rc = run_fc1(h, h->P, h->a_rows, fn, h1_rows(h, pend), st))) return rc;
-          pend += fn;
-        } else if ((rc = run_fc(h, h->P, h->a_rows, fn, y, st, h->c_rows))) {
-          return rc;
-        }
-        const int na = std::min(n_alt - f0, fn);   // alt rows of this slice: [f0, f0 + na)
-        if (na <= 0) continue;
-        if (f0 == 0) {
-          if ((rc = st_wait(h->pev[13]))) return rc;   // alt conv6 runs (and the Q reads of their patches)
-          // alt conv6 blocks into Q (conv5 rows are dead): only the rows the alt windows read
-          seg_alt_blocks<<<dim3(kAltRows6, (unsigned)nb), dim3(64), 0, st>>>(h->P, h->D0, n_ph, g.T6, h->seg_tab,
-                                                                            640 * eb / 16, h->Q);
-          if ((rc = check_launch("seg_alt_blocks"))) return rc;
-        }
-        long long* acrow = gather2 ? h->c_rows + h->fc2_rows : h->c_rows;   // alt rows apart
-        seg_a_rows<<<dim3((na + 255) / 256), dim3(256), 0, st>>>(
-            h->win_seg_d, h->win_off_d, win_row ? h->win_row_d : nullptr, widx + f0, 0, na, s0, ss, L, n_ph, phi,
-            g.T6, h->a_rows, acrow);
-        if ((rc = check_launch("seg_a_rows"))) return rc;
-        const unsigned* mask = nullptr;
-        double frac = 1.0;
-        if (planes_gemm()) {
-          const int tiles = (int)((na + gemm_bm() - 1) / gemm_bm());
-          unsigned* md = reinterpret_cast<unsigned*>(h->slab_mask);
-          EXPECTO_HIP_CHECK(hipMemsetAsync(md, 0, tiles * sizeof(unsigned), st));
-          fc1_slab_mask_seg<<<dim3((na + 255) / 256), dim3(256), 0, st>>>(
-              widx + f0, na, h->win_seg_d, h->win_off_d, s0, ss, L, phi, h->seg_tab, (int)gemm_bm(),
-              kFc1In / h->fc_splits, md);
-          if ((rc = check_launch("fc1_slab_mask_seg"))) return rc;
-          mask = md;
-          if (h->profiling) {   // executed share of the slabs, counted on the device (no sync)
-            if ((rc = count_slab_macs(h, md, tiles, na, st))) return rc;
-            frac = 0.0;
-          }
-        }
-        DeltaScope ds(h);
-        if (gather2) {
-          float* h1a = h1_rows(h, h->fc2_rows);
-          if ((rc = run_fc1(h, h->Q, h->a_rows, na, h1a, st, mask, frac, fn)) ||
-              (rc = run_fc2(h, h1a, na, pr->y_alt, st, acrow)))
-            return rc;
-        } else if ((rc = run_fc(h, h->Q, h->a_rows, na, pr->y_alt, st, h->c_rows, mask, frac, fn))) {
-          return rc;
-        }
-      }
-      if ((rc = flush2())) return rc;   // the ref rows are read by copy_rows below
-      if (pr) {
-        if (ic1 > ic0) {
-          copy_rows<<<dim3(ic1 - ic0), dim3(256), 0, st>>>(y, pr->y_alt, h->copy_w_d + ic0,
-                                                           win_row ? h->win_row_d : nullptr, n_win, ss.rc_rows);
-          if ((rc = check_launch("copy_rows"))) return rc;
-        }
-      }
-    }
-    if (pr && (rc = st_wait(h->pev[13]))) return rc;   // every alt run of the chunk joined
+  const SegGeo& g = pl.g;
+  const SegCall c{h, pl, st, (pr && h->st2) ? h->st2 : st, pr, SegDims{L, g.T1, g.P1, g.T3, g.T4, g.S5, g.T5, g.T6},
+                  make_int4(pl.ph[0], pl.ph[1], pl.ph[2], pl.ph[3]),
+                  make_int4(pl.ph_idx[0], pl.ph_idx[1], pl.ph_idx[2], pl.ph_idx[3]), act_bytes(), codes, code_stride,
+                  mode, y, win_row ? h->win_row_d : nullptr};
+  for (size_t ci = 0; ci < pl.chunks.size(); ++ci) {
+    const int s0 = pl.chunks[ci].first, s1 = pl.chunks[ci].second;
+    const SegChunk ck{ci, s0, s1 - s0, pl.vfirst[s0], pl.vfirst[s1] - pl.vfirst[s0], (long long)(s1 - s0) * pl.n_ph};
+    PQSwap pq{h, false};   // undoes seg_trunk's swap of P and Q when the chunk ends, however it ends
+    if ((rc = seg_trunk(c, ck, pq))) return rc;
+    if (ck.nw > 0 && (rc = pl.fkm ? seg_fc_karatsuba(c, ck) : seg_fc_direct(c, ck))) return rc;
+    if (pr && (rc = seg_st_wait(c, h->pev[13]))) return rc;   // every alt run of the chunk joined
   }
   return EXPECTO_OK;
 }
@@ -3487,15 +3326,9 @@ int forward_pairs(expecto_beluga* h, const uint8_t* ref, const uint8_t* alt, int
   // ref launch that wrote it) and the ref layer l+1 launch, which overwrites that buffer (ping-
   // pong), waits until the alt patch of layer l has been assembled.
   hipStream_t sa = h->st2 ? h->st2 : st;
-  auto order = [&](hipStream_t from, hipStream_t to, hipEvent_t e) -> int {
-    if (from == to) return EXPECTO_OK;
-    EXPECTO_HIP_CHECK(hipEventRecord(e, from));
-    EXPECTO_HIP_CHECK(hipStreamWaitEvent(to, e, 0));
-    return EXPECTO_OK;
-  };
   for (int v0 = 0; v0 < n; v0 += nv_max) {
     const int nv = std::min(nv_max, n - v0), R = strands * nv;
-    if ((rc = order(st, sa, h->pev[0]))) return rc;   // caller's inputs (and the previous chunk)
+    if ((rc = stream_order(st, sa, h->pev[0]))) return rc;   // caller's inputs (and the previous chunk)
     // conv1: ref windows (full; fused: inside the conv2 launch) and the alt runs (15 codes -> 8
     // rows; fused: the whole alt conv2 patch, kC1Pat codes -> kDA[2] rows)
     const bool kmer = use_kmer(h, nullptr);
@@ -3523,7 +3356,7 @@ int forward_pairs(expecto_beluga* h, const uint8_t* ref, const uint8_t* alt, int
     for (int l = 0; l < 5; ++l) {   // conv2..conv6 (layer index l+2 in the delta tables)
       const ConvGeo& g = kConv[l];
       const int L = l + 2;
-      if ((rc = order(st, sa, h->pev[1 + 2 * l]))) return rc;   // src (ref layer l-1) written
+      if ((rc = stream_order(st, sa, h->pev[1 + 2 * l]))) return rc;   // src (ref layer l-1) written
       const bool fused = l == 0 && fuse;   // the alt conv2 patch is already in DA
       const bool tab = l == 0 && kmer;     // conv2 from the k-mer table (ref windows and alt patches)
       if (tab)
@@ -3536,7 +3369,7 @@ int forward_pairs(expecto_beluga* h, const uint8_t* ref, const uint8_t* alt, int
         delta_assemble<<<dim3(R), dim3(256), 0, sa>>>(src, g.s_in, dprev, L, row16, nv, v0, var_pos, h->DA);
         if ((rc = check_launch("delta_assemble"))) return rc;
       }
-      if ((rc = order(sa, st, h->pev[2 + 2 * l]))) return rc;   // src read: ref l+1 may overwrite it
+      if ((rc = stream_order(sa, st, h->pev[2 + 2 * l]))) return rc;   // src read: ref l+1 may overwrite it
       DeltaScope ds(h);
       if (tab) {
         const C1Src fa{h->delta_codes, kC1PatStride, R, EXPECTO_STRAND_FWD, 0, kC1Pat};
@@ -3547,7 +3380,7 @@ int forward_pairs(expecto_beluga* h, const uint8_t* ref, const uint8_t* alt, int
       std::swap(src, dst);
       std::swap(dprev, dnext);
     }
-    if ((rc = order(sa, st, h->pev[11]))) return rc;   // alt conv6 runs done
+    if ((rc = stream_order(sa, st, h->pev[11]))) return rc;   // alt conv6 runs done
     float* act6 = src;   // ref conv6 rows; dprev = the alt runs' conv6 rows
     pair_rows<<<dim3((R + 255) / 256), dim3(256), 0, st>>>(h->c_rows, R, nv, v0, strand_stride);
     if ((rc = check_launch("pair_rows"))) return rc;

@@ -113,12 +113,14 @@ def _function_body(src: str, name: str) -> str:
 
 def test_production_forward_has_no_host_sync():
     """The forward paths only enqueue work: no stream/device sync and no blocking copy in the
-    functions a forward call runs (forward_chunk, forward_segments, forward_pairs, run_fc,
-    run_conv, run_conv1, stage_copies); the f16x3 overflow check syncs only in its per-call
-    mode (run_checked) and the deferred release point (expecto_beluga_overflow_pending)."""
+    functions a forward call runs (forward_chunk, forward_segments with its stage functions and
+    launch helpers, forward_pairs, run_fc, run_conv, run_conv1, stage_copies); the f16x3 overflow
+    check syncs only in its per-call mode (run_checked) and the deferred release point
+    (expecto_beluga_overflow_pending)."""
     src = open(os.path.join(REPO, "expecto_amd", "csrc", "beluga.hip")).read()
     for fn in ("forward_chunk", "forward_segments", "forward_pairs", "run_fc", "run_conv", "run_conv1",
-               "stage_copies", "count_slab_macs"):
+               "stage_copies", "count_slab_macs", "seg_trunk", "seg_fc_karatsuba", "seg_fc_direct", "stream_order",
+               "seg_alt_asm", "seg_alt_gemm", "seg_st_wait", "seg_rows", "seg_fc2", "seg_alt_conv6", "seg_copy_tail"):
         body = _function_body(src, fn)
         for bad in ("hipStreamSynchronize", "hipDeviceSynchronize", "hipMemcpy(", "hipMemcpyDeviceToHost"):
             assert bad not in body, (fn, bad)
