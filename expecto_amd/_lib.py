@@ -67,6 +67,9 @@ SIGNATURES = {
                                               c_vp, c_vp]),
     "expecto_variant_reduce_lut": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                   c_vp, ctypes.c_int, c_vp, c_vp]),
+    "expecto_variant_contrib": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                               c_vp, ctypes.c_int, c_vp, ctypes.c_int, c_vp, ctypes.c_int, c_vp, c_vp,
+                                               ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "expecto_gblinear_predict": (ctypes.c_int, [c_vp, ctypes.c_longlong, ctypes.c_longlong, c_vp, ctypes.c_int,
                                                 c_vp, ctypes.c_float, c_vp, c_vp]),
     "expecto_gblinear_train_round": (ctypes.c_int, [c_vp, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, ctypes.c_int,

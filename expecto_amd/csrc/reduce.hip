@@ -2,7 +2,8 @@
 //  * variant window generation from a device-resident genome (chromatin.py:175-209),
 //  * diff = alt - ref (chromatin.py:281), fwd/rc averaging (predict.py:186-190),
 //  * TSS spatial-transform reduction (compute_expecto_features.py:88-124),
-//  * variant spatial reduction (predict.py:87-136).
+//  * variant spatial reduction (predict.py:87-136),
+//  * attribution to marks and mark clusters (predict_by_cluster_rsat.py:105-144).
 #include <hip/hip_runtime.h>
 
 #include <string>
@@ -433,6 +434,130 @@ __global__ __launch_bounds__(kRowsPairs) void variant_reduce_rows_kernel(
   }
 }
 
+// ---- attribution of an expression effect to marks and mark clusters --------------------------
+// predict_by_cluster.py:73-109 / predict_by_cluster_rsat.py:105-144 (interpret_model,
+// interpret_model_with_clusters[_rsat]) on top of the spatial reduction of predict.py:87-136,
+// without the [n, 10*nfeat] feature matrices: one workgroup per variant keeps
+// D[k] = A[k] - R[k] (A, R: the alt and ref features, bitwise what variant_reduce_kernel stores)
+// of 2 marks per thread in registers and runs every model over them.
+//
+// wave_sum: the one summation order of every total, cluster sum and cluster denominator.  The
+// sum of x_0 .. x_{c-1} (c > 0): lane l of one wave adds x_l, x_{l+64}, x_{l+128}, ... in that
+// order starting from -0.0 (the first term as it is; a lane with no term keeps -0.0, and
+// y + -0.0 == y for every y), then the 64 lane sums fold as p[l] += p[l + s] for s = 32, 16, 8,
+// 4, 2, 1 (l < s); p[0] is the sum.  c == 0 gives +0.0.  The order depends on c alone.
+constexpr int kContribThreads = 1024;
+constexpr int kContribTile = 2 * kContribThreads;   // marks whose D one workgroup keeps in registers
+
+__device__ __forceinline__ double wave_sum(const double* x, const int* __restrict__ idx, int cnt, int lane) {
+#pragma clang fp contract(off)
+  if (cnt == 0) return 0.0;
+  double p = -0.0;
+  for (int i = lane; i < cnt; i += 64) p += x[idx ? idx[i] : i];
+  // lanes >= s add values that never reach lane 0
+  for (int s = 32; s > 0; s >>= 1) p += __shfl_down(p, s, 64);
+  return p;
+}
+
+// D[k] of feature column `col` of variant v: the products and sums of variant_reduce_kernel.
+__device__ __forceinline__ void contrib_diff(const float* __restrict__ eff_ref, const float* __restrict__ eff_alt,
+                                             int n_shift, int n, long long v, int nfeat, int col, const double* wsh,
+                                             double* D) {
+#pragma clang fp contract(off)
+  double a[10], r[10];
+#pragma unroll
+  for (int k = 0; k < 10; ++k) a[k] = r[k] = -0.0;
+  for (int j = 0; j < n_shift; ++j) {
+    const long long o = ((long long)j * n + v) * nfeat + col;
+    const double ea = (double)eff_alt[o], er = (double)eff_ref[o];
+#pragma unroll
+    for (int k = 0; k < 10; ++k) {
+      a[k] += ea * wsh[j * 10 + k];
+      r[k] += er * wsh[j * 10 + k];
+    }
+  }
+#pragma unroll
+  for (int k = 0; k < 10; ++k) D[k] = a[k] - r[k];
+}
+
+__device__ __forceinline__ double contrib_dot(const double* __restrict__ wm, int nk, int f, const double* D) {
+#pragma clang fp contract(off)
+  double c = wm[f] * D[0];
+#pragma unroll
+  for (int k = 1; k < 10; ++k) c += wm[(long long)k * nk + f] * D[k];
+  return c;
+}
+
+// grid: n workgroups of 1024 threads.  Dynamic LDS: the [n_shift][10] weights, one model's nk
+// contributions, its n_clu cluster sums, its total and cluster denominator.  Up to 2048 kept
+// marks the effects are read once and D stays in registers across the models; beyond that the
+// marks go in tiles of 2048 and every model recomputes each tile's D (same bits).
+__global__ __launch_bounds__(kContribThreads) void variant_contrib_kernel(
+    const float* __restrict__ eff_ref, const float* __restrict__ eff_alt, const long long* __restrict__ dist,
+    const uint8_t* __restrict__ strand_plus, const int* __restrict__ shifts, int n_shift, int n, int nfeat,
+    const double* __restrict__ lut, int lut_len, const int* __restrict__ keep, int nk, const double* __restrict__ w,
+    int n_models, const int* __restrict__ clu_ptr, const int* __restrict__ clu_mark, int n_clu,
+    double* __restrict__ contrib, double* __restrict__ total, double* __restrict__ prop, double* __restrict__ clu,
+    double* __restrict__ clu_prop) {
+#pragma clang fp contract(off)   // products rounded before the sum, as numpy
+  extern __shared__ double wsh[];   // [n_shift][10]
+  double* const cs = wsh + 10 * n_shift;   // [nk] contributions of the current model
+  double* const cl = cs + nk;              // [n_clu] its cluster sums
+  double* const sc = cl + n_clu;           // its total, its cluster denominator
+  const long long v = blockIdx.x;
+  const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
+  variant_weights_lds(dist, strand_plus, shifts, n_shift, v, lut, lut_len, wsh);
+  __syncthreads();
+  const int n_tiles = (nk + kContribTile - 1) / kContribTile;
+  double D0[10], D1[10];
+  for (int m = 0; m < n_models; ++m) {
+    const double* wm = w + (long long)m * 10 * nk;
+    const long long row = (long long)m * n + v;
+    for (int tile = 0; tile < n_tiles; ++tile) {
+      const int f0 = tile * kContribTile + t, f1 = f0 + kContribThreads;
+      if (m == 0 || n_tiles > 1) {
+        if (f0 < nk) contrib_diff(eff_ref, eff_alt, n_shift, n, v, nfeat, keep[f0], wsh, D0);
+        if (f1 < nk) contrib_diff(eff_ref, eff_alt, n_shift, n, v, nfeat, keep[f1], wsh, D1);
+      }
+      if (f0 < nk) {
+        const double c = contrib_dot(wm, nk, f0, D0);
+        cs[f0] = c;
+        if (contrib) contrib[row * nk + f0] = c;
+      }
+      if (f1 < nk) {
+        const double c = contrib_dot(wm, nk, f1, D1);
+        cs[f1] = c;
+        if (contrib) contrib[row * nk + f1] = c;
+      }
+    }
+    __syncthreads();
+    if (wave == 0) {
+      const double s = wave_sum(cs, nullptr, nk, lane);
+      if (lane == 0) sc[0] = s;
+    }
+    for (int c = wave; c < n_clu; c += kContribThreads / 64) {
+      const int b = clu_ptr[c];
+      const double s = wave_sum(cs, clu_mark + b, clu_ptr[c + 1] - b, lane);
+      if (lane == 0) cl[c] = s;
+    }
+    __syncthreads();
+    if (wave == 0 && n_clu > 0) {
+      const double s = wave_sum(cl, nullptr, n_clu, lane);
+      if (lane == 0) sc[1] = s;
+    }
+    const double tot = sc[0];
+    if (t == 0 && total) total[row] = tot;
+    if (prop)
+      for (int f = t; f < nk; f += kContribThreads) prop[row * nk + f] = cs[f] / tot;
+    __syncthreads();
+    for (int c = t; c < n_clu; c += kContribThreads) {
+      if (clu) clu[row * n_clu + c] = cl[c];
+      if (clu_prop) clu_prop[row * n_clu + c] = cl[c] / sc[1];
+    }
+    __syncthreads();   // cs, cl and sc are the next model's
+  }
+}
+
 }  // namespace expecto
 
 using namespace expecto;
@@ -610,6 +735,33 @@ int expecto_variant_reduce_lut(const float* effects, const long long* dist, cons
 int expecto_variant_reduce(const float* effects, const long long* dist, const uint8_t* strand_plus, const int* shifts,
                            int n_shift, int n, int nfeat, double* out, void* stream) {
   return expecto_variant_reduce_lut(effects, dist, strand_plus, shifts, n_shift, n, nfeat, nullptr, 0, out, stream);
+}
+
+// gfx950 has 160 KiB of LDS per CU; more than 64 KiB of it per workgroup is an opt-in.
+constexpr size_t kContribMaxLds = 160 * 1024;
+
+int expecto_variant_contrib(const float* eff_ref, const float* eff_alt, const long long* dist,
+                            const uint8_t* strand_plus, const int* shifts, int n_shift, int n, int nfeat,
+                            const double* exp_lut, int lut_len, const int* keep, int nk, const double* w, int n_models,
+                            const int* clu_ptr, const int* clu_mark, int n_clu, double* contrib, double* total,
+                            double* prop, double* clu, double* clu_prop, void* stream) {
+  EXPECTO_REQUIRE(n >= 0 && n_shift > 0 && n_shift <= kMaxShifts && nfeat > 0, "bad shape (n_shift <= 819)");
+  EXPECTO_REQUIRE(nk >= 1 && nk <= nfeat && n_models >= 1 && n_clu >= 0, "bad shape (1 <= nk <= nfeat, n_models >= 1)");
+  if (n == 0) return EXPECTO_OK;
+  EXPECTO_REQUIRE(n <= 65535, "at most 65535 variants per call");
+  EXPECTO_REQUIRE(eff_ref && eff_alt && dist && strand_plus && shifts && keep && w, "null argument");
+  EXPECTO_REQUIRE(n_clu == 0 || (clu_ptr && clu_mark), "null argument (clusters)");
+  EXPECTO_REQUIRE(!exp_lut || lut_len > 0, "empty exp table");
+  if (!clu && !clu_prop) n_clu = 0;
+  const size_t shm = (10 * (size_t)n_shift + (size_t)nk + (size_t)n_clu + 2) * sizeof(double);
+  EXPECTO_REQUIRE(shm <= kContribMaxLds, "shifts, kept marks and clusters exceed the 160 KiB of LDS");
+  if (shm > 65536)
+    EXPECTO_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(variant_contrib_kernel),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)kContribMaxLds));
+  variant_contrib_kernel<<<dim3(n), dim3(kContribThreads), shm, as_stream(stream)>>>(
+      eff_ref, eff_alt, dist, strand_plus, shifts, n_shift, n, nfeat, exp_lut, lut_len, keep, nk, w, n_models, clu_ptr,
+      clu_mark, n_clu, contrib, total, prop, clu, clu_prop);
+  return check_launch("variant_contrib");
 }
 
 int expecto_gblinear_predict(const double* X, long long n, long long ld, const int* cols, int ncols, const float* w,

@@ -5,8 +5,12 @@
 * ``fwd_rc_average``: ``predict.py:186-190`` ``(x[:N] + x[N:]) / 2``.
 * ``variant_features``: ``predict.py:87-136`` -- exp(-c*floor(|d|/200)) weights per shift,
   split by upstream/downstream, summed over shifts into ``[n, 10*2002]`` float64.
+* ``variant_contributions``: ``predict_by_cluster_rsat.py:105-144`` -- the expression effect
+  split by mark and by mark cluster, for any number of models in one pass over the effects.
 """
 from __future__ import annotations
+
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -84,6 +88,91 @@ def variant_reduce(effects: torch.Tensor, tables: tuple, out: torch.Tensor | Non
         _lib.check(lib.expecto_variant_reduce_lut(_lib.dptr(eff), _lib.dptr(d[v0:v1]), _lib.dptr(sp[v0:v1]),
                                                   _lib.dptr(sh), S, v1 - v0, F, _lib.dptr(lut), lut.shape[1],
                                                   _lib.dptr(out[v0:v1]), _lib.stream_ptr()), "variant_reduce")
+    return out
+
+
+Contributions = namedtuple("Contributions", "contrib total prop clu clu_prop")
+
+
+def clusters_csr(clusters, nk: int) -> tuple:
+    """Lists of mark indices (0..nk-1), one per cluster -> CSR (ptr int32[n_clu+1], mark int32[...])."""
+    ptr = np.zeros(len(clusters) + 1, np.int32)
+    ptr[1:] = np.cumsum([len(c) for c in clusters])
+    mark = np.asarray([i for c in clusters for i in c], np.int32).reshape(-1)
+    if mark.size and (mark.min() < 0 or mark.max() >= nk):
+        raise RuntimeError(f"variant_contributions: cluster members must index the {nk} kept marks")
+    return ptr, mark
+
+
+def variant_contributions(eff_ref: torch.Tensor, eff_alt: torch.Tensor, dist, strand_plus, shifts, keep_idx, weights,
+                          clusters=None, outputs=None) -> Contributions:
+    """Per-mark and per-cluster attribution of the expression effect
+    (``predict_by_cluster_rsat.py:105-144``), fused with the spatial reduction
+    (``expecto_variant_contrib``; include/expecto_hip.h states the summation order).
+
+    eff_ref, eff_alt ``[S, n, F]`` fp32 (device, fwd/rc averaged, shift order); dist, strand_plus,
+    shifts as ``variant_features``; keep_idx: the kept mark columns, ascending; weights
+    ``[n_models, 10*nk]`` (or ``[10*nk]``) float64 as ``GBLinear.dump_weights`` gives them;
+    clusters: lists of indices into the kept marks, or None.  Returns float64 device tensors
+    ``contrib [M, n, nk]``, ``total [M, n]``, ``prop [M, n, nk]``, ``clu`` and ``clu_prop``
+    ``[M, n, n_clu]`` (None without clusters); one launch per 65,535 variants.  outputs: the
+    names of the tensors wanted (default: all); the others are neither allocated nor written
+    and come back as None."""
+    lib = _lib.load()
+    S, n, F = eff_ref.shape
+    if eff_alt.shape != eff_ref.shape or eff_ref.dtype != torch.float32 or eff_alt.dtype != torch.float32:
+        raise RuntimeError("variant_contributions: eff_ref and eff_alt must be fp32 tensors of one shape")
+    dev = eff_ref.device
+    keep = np.ascontiguousarray(keep_idx, np.int32).reshape(-1)
+    nk = keep.size
+    if nk == 0 or keep.min() < 0 or keep.max() >= F or np.any(np.diff(keep) <= 0):
+        raise RuntimeError("variant_contributions: keep_idx must be ascending mark columns")
+    w = torch.as_tensor(weights, dtype=torch.float64).reshape(-1, 10 * nk).contiguous().to(dev)
+    M = w.shape[0]
+    if M == 0:
+        raise RuntimeError("variant_contributions: no model weights")
+    d, sp, sh, lut = variant_tables(dist, strand_plus, shifts, dev)
+    if d.shape != (n,) or sp.shape != (n,) or sh.shape != (S,):
+        raise RuntimeError("variant_contributions: table shapes do not match the effects")
+    keep_d = torch.from_numpy(keep).to(dev)
+    n_clu, ptr_d, mark_d = 0, None, None
+    if clusters is not None:
+        ptr, mark = clusters_csr(clusters, nk)
+        n_clu = len(ptr) - 1
+        ptr_d = torch.from_numpy(ptr).to(dev)
+        mark_d = torch.from_numpy(np.concatenate([mark, np.zeros(1, np.int32)])).to(dev)   # never empty
+    eff_ref, eff_alt = eff_ref.contiguous(), eff_alt.contiguous()
+    wanted = set(Contributions._fields if outputs is None else outputs)
+    if not wanted <= set(Contributions._fields):
+        raise RuntimeError(f"variant_contributions: outputs are among {Contributions._fields}")
+    if not n_clu:
+        wanted -= {"clu", "clu_prop"}
+
+    def alloc(rows):
+        shapes = {"contrib": (M, rows, nk), "total": (M, rows), "prop": (M, rows, nk), "clu": (M, rows, n_clu),
+                  "clu_prop": (M, rows, n_clu)}
+        return Contributions(*[torch.empty(shapes[k], dtype=torch.float64, device=dev) if k in wanted else None
+                               for k in Contributions._fields])
+
+    def optr(t):
+        return None if t is None else _lib.dptr(t)
+
+    out = alloc(n)
+    for v0 in range(0, n, 65535):
+        v1 = min(n, v0 + 65535)
+        whole = v0 == 0 and v1 == n
+        er, ea = (eff_ref, eff_alt) if whole else (eff_ref[:, v0:v1].contiguous(), eff_alt[:, v0:v1].contiguous())
+        part = out if whole else alloc(v1 - v0)       # the kernel's rows are m * (v1 - v0) + v
+        _lib.check(lib.expecto_variant_contrib(
+            _lib.dptr(er), _lib.dptr(ea), _lib.dptr(d[v0:v1]), _lib.dptr(sp[v0:v1]), _lib.dptr(sh), S, v1 - v0, F,
+            _lib.dptr(lut), lut.shape[1], _lib.dptr(keep_d), nk, _lib.dptr(w), M,
+            _lib.dptr(ptr_d) if n_clu else None, _lib.dptr(mark_d) if n_clu else None, n_clu,
+            optr(part.contrib), optr(part.total), optr(part.prop), optr(part.clu), optr(part.clu_prop),
+            _lib.stream_ptr()), "variant_contrib")
+        if not whole:
+            for dst, src in zip(out, part):
+                if dst is not None:
+                    dst[:, v0:v1] = src
     return out
 
 

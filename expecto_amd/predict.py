@@ -69,8 +69,11 @@ def build_parser():
 
 
 def get_keep_mask(beluga_features_df, no_tf_features, no_dnase_features, no_histone_features,
-                  intersect_with_lambert, no_pol2):
-    """cluster_utils.py:8-50 (same filters, same messages)."""
+                  intersect_with_lambert, no_pol2, return_hgnc_df=False):
+    """cluster_utils.py:8-50 (same filters, same messages).  With ``return_hgnc_df`` it returns
+    ``(keep_mask, hgnc_df)`` ahead of the count message, as the reference does; ``hgnc_df`` is the
+    feature table with HGNC-mapped assay names, or None without ``intersect_with_lambert``."""
+    hgnc_df = None
     keep_mask = np.ones(beluga_features_df.shape[0], dtype=bool)
     if no_tf_features:
         print("not including TF features")
@@ -93,12 +96,16 @@ def get_keep_mask(beluga_features_df, no_tf_features, no_dnase_features, no_hist
                     match = match[match["Match type"] == "Approved symbol"].iloc[0]
                 assays[i] = match["Approved symbol"].upper()
         hgnc = pd.Series(assays, index=beluga_features_df.index)
+        hgnc_df = beluga_features_df.copy()
+        hgnc_df["Assay"] = assays
         keep_mask = keep_mask & hgnc.isin(lambert_df['Approved symbol'].values).values
         keep_mask = keep_mask & ~hgnc.isnull().values
     if no_pol2:
         print("taking out Pol2*")
         keep_mask = keep_mask & ~(beluga_features_df['Assay'].str.startswith('Pol'))
     keep_mask = np.asarray(keep_mask, dtype=bool)
+    if return_hgnc_df:
+        return keep_mask, hgnc_df
     print(f"Number of features included in model: {np.sum(keep_mask)}")
     return keep_mask
 
@@ -124,21 +131,32 @@ def load_effects(pattern: str, shifts, dev) -> dict:
     return {k: torch.stack(v, 0) for k, v in out.items()}      # [S, N, F]
 
 
-def run(args) -> pd.DataFrame:
-    os.makedirs(args.out_dir, exist_ok=True)
-    dev = torch.device("cuda", torch.cuda.current_device())
-    beluga_features_df = pd.read_csv(args.belugaFeatures, sep='\t', index_col=0)
+def read_features_table(path: str) -> pd.DataFrame:
+    """predict.py:58-60."""
+    beluga_features_df = pd.read_csv(path, sep='\t', index_col=0)
     beluga_features_df['Assay type + assay + cell type'] = (beluga_features_df['Assay type'] + '/' +
                                                            beluga_features_df['Assay'] + '/' +
                                                            beluga_features_df['Cell type'])
-    mask_args = (args.no_tf_features, args.no_dnase_features, args.no_histone_features,
-                 args.intersect_with_lambert, args.no_pol2)
-    keep_mask = get_keep_mask(beluga_features_df, *mask_args)          # predict.py:61-62
-    model = GBLinear.load(args.model_save_file.strip(), base_score=args.base_score)
-    maxshift = int(args.maxshift)
-    shifts = shift_order(maxshift)
-    eff = load_effects(args.snpEffectFilePattern, shifts, dev)
+    return beluga_features_df
 
+
+def mask_arguments(args) -> tuple:
+    return (args.no_tf_features, args.no_dnase_features, args.no_histone_features,
+            args.intersect_with_lambert, args.no_pol2)
+
+
+class Rows:
+    """The scored rows (predict.py:197-235): duplicate chromatin rows masked, every kept row
+    repeated per associated gene.  ``coor``: the repeated coordinate table; ``ridx``: each row's
+    index into the ``.diff.h5`` rows (device, int64); ``dist``, ``genename``, ``strand``: per row."""
+
+    def __init__(self, args, dev):
+        self.coor, self.ridx, self.dist, self.genename, self.strand = _load_rows(args, dev)
+        self.n = len(self.genename)
+        self.strand_plus = self.strand == '+'
+
+
+def _load_rows(args, dev):
     coor = pd.read_csv(args.coorFile_chromatin, sep='\t', header=None, comment='#')
     gene = pd.read_csv(args.geneFile, sep='\t', header=None, comment='#')
     gene = gene.drop_duplicates(keep="first")
@@ -161,47 +179,80 @@ def run(args) -> pd.DataFrame:
         dist = np.full(n, args.fixeddist, dtype=np.int64) if n else np.zeros(0, np.int64)
     genename = np.asarray(gene.iloc[geneinds, -2])
     strand = np.asarray(gene.iloc[geneinds, -3])
+    return coor, ridx, dist, genename, strand
 
-    keep_idx = np.nonzero(keep_mask)[0].astype(np.int32)
+
+def score_rows(args, models, eff, rows, keep_idx, shifts, batch_messages, dev):
+    """REF and ALT of every row for each model (predict.py:118-160): float64 ``[len(models), n]``
+    arrays.  ``batch_messages()`` prints what the reference prints ahead of the loop and in every
+    batch."""
     n_keep = len(keep_idx)
-    if model.num_feature != 10 * n_keep:
-        raise ValueError(f"model has {model.num_feature} features, the keep mask gives 10 x {n_keep}")
+    for model in models:
+        if model.num_feature != 10 * n_keep:
+            raise ValueError(f"model has {model.num_feature} features, the keep mask gives 10 x {n_keep}")
     cols = torch.from_numpy((np.arange(10, dtype=np.int32)[:, None] * args.nfeatures + keep_idx[None, :])
                             .reshape(-1).astype(np.int32)).to(dev)
-    strand_plus = strand == '+'
-    ref = np.zeros(n)
-    alt = np.zeros(n)
+    n = rows.n
+    ref = np.zeros((len(models), n))
+    alt = np.zeros((len(models), n))
     bs = int(args.batchSize)
-    get_keep_mask(beluga_features_df, *mask_args)                      # predict.py:118 (messages)
+    batch_messages(False)                                              # predict.py:118 (messages)
     for i in range(int((n - 1) / bs) + 1):                             # predict.py:122-160
         print("Processing " + str(i) + "th batch of " + str(bs))
-        get_keep_mask(beluga_features_df, *mask_args)                  # predict.py:138 (messages)
+        batch_messages(True)                                           # predict.py:138 (messages)
         lo, hi = i * bs, min(n, (i + 1) * bs)
         if hi <= lo:
             continue
-        sel = ridx[lo:hi]
-        preds = {}
-        for k in ("ref", "alt"):
-            x = variant_features(eff[k][:, sel], dist[lo:hi], strand_plus[lo:hi], shifts)
-            preds[k] = model.predict(x, cols).cpu().numpy()
-        ref[lo:hi] = preds["ref"]
-        alt[lo:hi] = preds["alt"]
+        sel = rows.ridx[lo:hi]
+        for k, dst in (("ref", ref), ("alt", alt)):
+            x = variant_features(eff[k][:, sel], rows.dist[lo:hi], rows.strand_plus[lo:hi], shifts)
+            for m, model in enumerate(models):
+                dst[m, lo:hi] = model.predict(x, cols).cpu().numpy()
+    return ref, alt
 
-    df = coor
-    df['dist'] = dist
-    df['gene'] = genename
-    df['strand'] = strand
-    df = pd.concat([df.reset_index(), pd.DataFrame(ref, columns=['REF']), pd.DataFrame(alt, columns=['ALT']),
-                    pd.DataFrame(alt - ref, columns=['SED'])], axis=1, ignore_index=False)
-    df.to_csv(f'{args.out_dir}/sed.tsv', header=True, sep='\t', index=False)
+
+def sed_frame(rows, ref, alt) -> pd.DataFrame:
+    """predict.py:237-251: the coordinate table with dist, gene, strand, REF, ALT and SED."""
+    df = rows.coor.copy()
+    df['dist'] = rows.dist
+    df['gene'] = rows.genename
+    df['strand'] = rows.strand
+    return pd.concat([df.reset_index(), pd.DataFrame(ref, columns=['REF']), pd.DataFrame(alt, columns=['ALT']),
+                      pd.DataFrame(alt - ref, columns=['SED'])], axis=1, ignore_index=False)
+
+
+def with_proportion(df: pd.DataFrame) -> pd.DataFrame:
+    out = df.copy()
+    out['SED_PROPORTION'] = np.abs(out['SED'] / ((out['REF'] + out['ALT']) / 2))
+    return out
+
+
+def write_sorted(df: pd.DataFrame, out_dir: str, ext: str = "tsv") -> None:
+    """predict.py:255-280: the copies sorted by |SED| and by |SED| / mean(REF, ALT)."""
     by_mag = df.copy()
     by_mag['SED_MAGNITUDES'] = np.abs(by_mag['SED'])
     by_mag = by_mag.sort_values(by='SED_MAGNITUDES', axis=0, ascending=False)
-    by_mag.to_csv(f'{args.out_dir}/sed_sorted_by_magnitude.tsv', header=True, sep='\t', index=False)
-    by_prop = df.copy()
-    by_prop['SED_PROPORTION'] = np.abs(by_prop['SED'] / ((by_prop['REF'] + by_prop['ALT']) / 2))
-    by_prop = by_prop.sort_values(by='SED_PROPORTION', axis=0, ascending=False)
-    by_prop.to_csv(f'{args.out_dir}/sed_sorted_by_proportion.tsv', header=True, sep='\t', index=False)
+    by_mag.to_csv(f'{out_dir}/sed_sorted_by_magnitude.{ext}', header=True, sep='\t', index=False)
+    by_prop = with_proportion(df).sort_values(by='SED_PROPORTION', axis=0, ascending=False)
+    by_prop.to_csv(f'{out_dir}/sed_sorted_by_proportion.{ext}', header=True, sep='\t', index=False)
+
+
+def run(args) -> pd.DataFrame:
+    os.makedirs(args.out_dir, exist_ok=True)
+    dev = torch.device("cuda", torch.cuda.current_device())
+    beluga_features_df = read_features_table(args.belugaFeatures)
+    mask_args = mask_arguments(args)
+    keep_mask = get_keep_mask(beluga_features_df, *mask_args)          # predict.py:61-62
+    model = GBLinear.load(args.model_save_file.strip(), base_score=args.base_score)
+    shifts = shift_order(int(args.maxshift))
+    eff = load_effects(args.snpEffectFilePattern, shifts, dev)
+    rows = Rows(args, dev)
+    keep_idx = np.nonzero(keep_mask)[0].astype(np.int32)
+    ref, alt = score_rows(args, [model], eff, rows, keep_idx, shifts,
+                          lambda in_batch: get_keep_mask(beluga_features_df, *mask_args), dev)
+    df = sed_frame(rows, ref[0], alt[0])
+    df.to_csv(f'{args.out_dir}/sed.tsv', header=True, sep='\t', index=False)
+    write_sorted(df, args.out_dir)
     return df
 
 

@@ -180,6 +180,12 @@ class GBLinear:
         with open(path, "w") as f:
             f.write("\n".join(lines) + "\n")
 
+    def dump_weights(self) -> np.ndarray:
+        """The weights as the reference's interpretation step reads them
+        (``predict_by_cluster.py:74-76``: ``float()`` of every weight line of ``model.get_dump()``):
+        float64, at the ``%g`` precision of ``save_dump``."""
+        return np.array([float("%g" % float(w)) for w in self.weights.reshape(-1)], dtype=np.float64)
+
     # -- scoring ------------------------------------------------------------------------
     def predict(self, X, cols=None, group: int = 0, out=None):
         """GPU gblinear margin of rows of X (float64 [n, ld] device tensor): feature j of a row

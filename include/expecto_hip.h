@@ -28,6 +28,8 @@
  *                                   0.5*(fwd+rc) of compute_expecto_features.py:123)
  *   expecto_tss_reduce             pos_weights x pred_fwd_rc (compute_expecto_features.py:91-124)
  *   expecto_variant_reduce(_lut)   exp-decay shift weights x effects (predict.py:87-136)
+ *   expecto_variant_contrib        per-mark and per-cluster attribution of the expression effect
+ *                                  (predict_by_cluster.py:73-109, predict_by_cluster_rsat.py:105-144)
  *   expecto_gblinear_predict       xgboost gblinear scoring of feature rows (predict.py:150-166)
  *   expecto_gblinear_train_round   one xgb.train boosting round of gblinear / reg:linear models
  *                                  (train.py:140-146, train_bootstrap.py:88-106)
@@ -295,6 +297,36 @@ int expecto_variant_reduce(const float* effects, const long long* dist, const ui
 int expecto_variant_reduce_lut(const float* effects, const long long* dist, const uint8_t* strand_plus,
                                const int* shifts, int n_shift, int n, int nfeat, const double* exp_lut, int lut_len,
                                double* out, void* stream);
+
+/* Attribution of the expression effect to chromatin marks and mark clusters
+ * (predict_by_cluster.py:73-109, predict_by_cluster_rsat.py:105-144), fused with the variant
+ * reduction so that the [n, 10*nfeat] feature matrices never exist.  Every pointer is a DEVICE
+ * pointer.  eff_ref, eff_alt, dist, strand_plus, shifts, exp_lut, lut_len: as
+ * expecto_variant_reduce_lut (same n_shift and n limits).  keep[nk]: the kept mark columns,
+ * ascending, each in 0..nfeat-1.  w[n_models, 10*nk] f64: the weights as the reference parses
+ * them from the text dump, index k*nk + f.  Clusters in CSR form: cluster c holds the marks
+ * clu_mark[clu_ptr[c] .. clu_ptr[c+1]), each in 0..nk-1; a mark may sit in several clusters, a
+ * cluster may be empty, n_clu = 0 skips the cluster outputs.  Outputs (f64, each may be NULL):
+ *   contrib[n_models, n, nk], total[n_models, n], prop[n_models, n, nk],
+ *   clu[n_models, n, n_clu], clu_prop[n_models, n, n_clu].
+ * Arithmetic, every product and sum rounded on its own (no FMA):
+ *   A[k], R[k]    the alt / ref features of mark f at decay row k, bitwise what
+ *                 expecto_variant_reduce_lut stores at [v, k*nfeat + keep[f]];
+ *   D[k]          A[k] - R[k];
+ *   contrib       w[m][0*nk+f]*D[0] + w[m][1*nk+f]*D[1] + ... + w[m][9*nk+f]*D[9], left to right;
+ *   total         S(contrib[m,v,0..nk-1]);
+ *   clu[c]        S(contrib[m,v,mark]) over the cluster's marks in clu_mark order;
+ *   prop          contrib / total;   clu_prop[c] = clu[c] / S(clu[m,v,0..n_clu-1])
+ * (IEEE divisions: a zero denominator gives nan or inf).  S(x_0 .. x_{c-1}) is one fixed order
+ * that depends on c alone: p[l] = x_l + x_{l+64} + x_{l+128} + ... left to right for l = 0..63
+ * (-0.0 where there is no term), then p[l] += p[l+s] for l < s, for s = 32, 16, 8, 4, 2, 1;
+ * S = p[0]; S of nothing is +0.0.  No atomics: results do not depend on n, n_models or the grid.
+ * 8 * (10*n_shift + nk + n_clu + 2) bytes of LDS must fit 160 KiB, else EXPECTO_EINVAL. */
+int expecto_variant_contrib(const float* eff_ref, const float* eff_alt, const long long* dist,
+                            const uint8_t* strand_plus, const int* shifts, int n_shift, int n, int nfeat,
+                            const double* exp_lut, int lut_len, const int* keep, int nk, const double* w, int n_models,
+                            const int* clu_ptr, const int* clu_mark, int n_clu, double* contrib, double* total,
+                            double* prop, double* clu, double* clu_prop, void* stream);
 
 /* Shift reduction of per-sequence window predictions (fwd and rc [n, n_shift, nfeat] f32, DEVICE)
  * with exp-decay weights [10, n_shift] f64 into float64 features, shifts summed in order.
