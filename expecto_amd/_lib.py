@@ -82,6 +82,9 @@ SIGNATURES = {
                                              ctypes.c_int, c_vp, c_vp]),
     "expecto_shift_reduce": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                             c_vp, c_vp]),
+    "expecto_pairwise_euclidean": (ctypes.c_int, [c_vp, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong,
+                                                  c_vp, c_vp]),
+    "expecto_ward_linkage": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp, c_vp, c_vp]),
     "expecto_last_error": (ctypes.c_char_p, []),
     "expecto_version": (ctypes.c_char_p, []),
 }

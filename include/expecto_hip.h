@@ -37,6 +37,9 @@
  *   expecto_gblinear_rmse          the eval-rmse / train-rmse of xgb.train's evallist (train.py:144-146)
  *   expecto_shift_reduce           200-shift reduction of consensus / eQTL sequences
  *                                  (geuvadis_sed_for_top_eqtls.py:95-121, geuvadis_predict_consensus.py:110-128)
+ *   expecto_pairwise_euclidean     scipy's pdist under AgglomerativeClustering().fit
+ *   expecto_ward_linkage           and its Ward linkage (interpret_features.py:99-120,
+ *                                  interpret_features_grouped.py:103-146)
  *   expecto_beluga_destroy         (model teardown)
  */
 #ifndef EXPECTO_HIP_H
@@ -381,6 +384,25 @@ int expecto_gblinear_predict_cols(const float* X, long long ld, int n, int num_f
  * above, out float64[n_models]. */
 int expecto_gblinear_rmse(const float* pred, const float* y, long long y_stride, const float* h, long long h_stride,
                           int n, int n_models, double* out, void* stream);
+
+/* Ward clustering of the chromatin marks over the training genes (interpret_features.py:99-120,
+ * interpret_features_grouped.py:103-146: sklearn's AgglomerativeClustering, i.e. scipy's pdist and
+ * its NN-chain Ward linkage), in two steps.
+ *
+ * Distances, on the device: X is n points of d dimensions, row-major with row stride ld >= d (DEVICE);
+ * out (DEVICE) receives the n(n-1)/2 Euclidean distances in scipy's condensed order, pair (i < j) at
+ * n*i - i*(i+1)/2 + (j-i-1).  Per pair: s = 0; for k = 0..d-1 in order t = X[i,k] - X[j,k],
+ * s = s + t*t (product and sum rounded separately, no FMA); out = sqrt(s) correctly rounded -- the
+ * loop of scipy.spatial.distance.pdist, so the bits are scipy's.  The padding X[., d..ld-1] is never
+ * read.  n < 2 writes nothing; d = 0 writes +0.0 everywhere.  n <= 2097152. */
+int expecto_pairwise_euclidean(const double* X, long long n, long long d, long long ld, double* out, void* stream);
+
+/* Linkage, on the HOST (no device call): scipy.cluster.hierarchy.linkage(condensed, 'ward') bit for
+ * bit.  condensed: the n(n-1)/2 distances in HOST memory, overwritten.  Merge i (ascending height,
+ * ties in NN-chain order) joins clusters children[2i] < children[2i+1] (ids < n are points, n + m is
+ * the cluster merge m made) at heights[i] into sizes[i] points.  n < 2, a NaN distance or a point
+ * with no finite distance to any other is refused (EXPECTO_EINVAL). */
+int expecto_ward_linkage(double* condensed, int n, int* children, double* heights, int* sizes);
 
 const char* expecto_last_error(void);
 const char* expecto_version(void);
