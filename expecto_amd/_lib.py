@@ -85,6 +85,19 @@ SIGNATURES = {
     "expecto_pairwise_euclidean": (ctypes.c_int, [c_vp, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong,
                                                   c_vp, c_vp]),
     "expecto_ward_linkage": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp, c_vp, c_vp]),
+    "expecto_tfidf_stats": (ctypes.c_int, [c_vp, ctypes.c_longlong, ctypes.c_longlong, c_vp, ctypes.c_int, c_vp, c_vp,
+                                           c_vp]),
+    "expecto_tfidf_gram_parts": (ctypes.c_int, [ctypes.c_int, ctypes.c_longlong]),
+    "expecto_tfidf_gram_workspace": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_longlong]),
+    "expecto_tfidf_gram": (ctypes.c_int, [c_vp, ctypes.c_longlong, ctypes.c_longlong, c_vp, ctypes.c_int, c_vp, c_vp,
+                                          c_vp, ctypes.c_size_t, c_vp]),
+    "expecto_tfidf_project": (ctypes.c_int, [c_vp, ctypes.c_longlong, ctypes.c_longlong, c_vp, ctypes.c_int, c_vp,
+                                             c_vp, ctypes.c_int, c_vp, ctypes.c_longlong, c_vp]),
+    "expecto_tfidf_transform_parts": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, ctypes.c_longlong]),
+    "expecto_tfidf_transform_workspace": (ctypes.c_size_t, [ctypes.c_int, ctypes.c_int, ctypes.c_longlong]),
+    "expecto_tfidf_transform": (ctypes.c_int, [c_vp, ctypes.c_longlong, ctypes.c_longlong, c_vp, ctypes.c_int, c_vp,
+                                               c_vp, ctypes.c_longlong, ctypes.c_int, c_vp, c_vp, ctypes.c_size_t,
+                                               c_vp]),
     "expecto_last_error": (ctypes.c_char_p, []),
     "expecto_version": (ctypes.c_char_p, []),
 }

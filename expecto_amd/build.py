@@ -6,7 +6,7 @@ import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCES = [os.path.join(HERE, "csrc", f) for f in ("beluga.hip", "reduce.hip", "train.hip", "cluster.hip")]
+SOURCES = [os.path.join(HERE, "csrc", f) for f in ("beluga.hip", "reduce.hip", "train.hip", "cluster.hip", "svd.hip")]
 OUT = os.path.join(HERE, "libexpecto_hip.so")
 ARCH = os.environ.get("EXPECTO_OFFLOAD_ARCH", "gfx950")
 
@@ -22,7 +22,7 @@ def needs_build() -> bool:
     if not os.path.exists(OUT):
         return True
     t = os.path.getmtime(OUT)
-    deps = SOURCES + [os.path.join(HERE, "csrc", h) for h in ("common.h", "gemm_kernel.h", "seg_plan.h", "ward_linkage.h")] + [
+    deps = SOURCES + [os.path.join(HERE, "csrc", h) for h in ("common.h", "gemm_kernel.h", "seg_plan.h", "ward_linkage.h", "tri_tiles.h")] + [
                       os.path.join(os.path.dirname(HERE), "include", "expecto_hip.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 

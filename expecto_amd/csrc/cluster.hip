@@ -6,6 +6,7 @@
 #include <string>
 
 #include "common.h"
+#include "tri_tiles.h"
 #include "ward_linkage.h"
 
 namespace expecto {
@@ -20,22 +21,7 @@ constexpr int PD_LDW = PD_KS + 1;   // LDS row stride in doubles: odd, so 16 poi
 constexpr int PD_THREADS = 256;
 constexpr long long PD_MAX_N = 1LL << 21;   // the tile count of the upper triangle stays below 2^31
 
-// Tiles per tile-row r of the upper triangle: T - r (columns r .. T-1); tiles before row r.
-__device__ inline long long pd_row_start(long long r, long long T) { return r * T - r * (r - 1) / 2; }
-
-// Tile (bi <= bj) of linear upper-triangle tile index t.
-__device__ inline void pd_tile_of(long long t, long long T, int& bi, int& bj) {
-  const double b = 2.0 * (double)T + 1.0;
-  long long r = (long long)((b - sqrt(b * b - 8.0 * (double)t)) * 0.5);
-  r = r < 0 ? 0 : (r > T - 1 ? T - 1 : r);
-#pragma unroll
-  for (int fix = 0; fix < 2; ++fix) {   // the estimate is within one row of the answer
-    if (r > 0 && pd_row_start(r, T) > t) --r;
-    if (r < T - 1 && pd_row_start(r + 1, T) <= t) ++r;
-  }
-  bi = (int)r;
-  bj = (int)(r + (t - pd_row_start(r, T)));
-}
+// The tile (bi <= bj) of a workgroup's linear index: pd_tile_of, tri_tiles.h.
 
 // out[pair (i < j)] = sqrt(sum_k (X[i,k] - X[j,k])^2): s = 0, then s = s + t*t for k = 0..d-1 in
 // order, the product and the sum rounded separately, the square root correctly rounded -- scipy's

@@ -40,6 +40,9 @@
  *   expecto_pairwise_euclidean     scipy's pdist under AgglomerativeClustering().fit
  *   expecto_ward_linkage           and its Ward linkage (interpret_features.py:99-120,
  *                                  interpret_features_grouped.py:103-146)
+ *   expecto_tfidf_stats / _gram    tf-idf of the mark tracks and its float64 Gram matrix (svd.py:76-85)
+ *   expecto_tfidf_project          components_ of the truncated SVD (svd.py:84-85)
+ *   expecto_tfidf_transform        svd.transform(tf_idf) (svd_transform.py:80)
  *   expecto_beluga_destroy         (model teardown)
  */
 #ifndef EXPECTO_HIP_H
@@ -403,6 +406,48 @@ int expecto_pairwise_euclidean(const double* X, long long n, long long d, long l
  * the cluster merge m made) at heights[i] into sizes[i] points.  n < 2, a NaN distance or a point
  * with no finite distance to any other is refused (EXPECTO_EINVAL). */
 int expecto_ward_linkage(double* condensed, int n, int* children, double* heights, int* sizes);
+
+/* Truncated SVD of the tf-idf mark tracks (svd.py:58-85, svd_transform.py:49-81), by the float64 Gram
+ * matrix of the tf-idf rows; its eigenproblem is the caller's (expecto_amd/svd.py, on the host).
+ *
+ * Shared by the four entry points.  D (DEVICE) is one chunk of n columns of the track matrix as the
+ * per-gene files hold them: float32 [n, ld], marks contiguous.  keep_idx (DEVICE) int32[m]: the kept
+ * marks, distinct, in any order, every entry in [0, ld) (not checked; ld >= m is).  x[n,i] =
+ * D[n, keep_idx[i]]; every other element of D is never read.  All arithmetic is float64:
+ *   c_n = sum_i x[n,i] (i ascending), idf_n = log(m / (1 + c_n)), r_i = sum_n x[n,i], t[n,i] = x[n,i] idf_n.
+ * No atomics: every sum has a fixed order, so two identical calls give identical bits.  n = 0 or
+ * m = 0 (or k = 0) is a no-op that writes nothing.  m <= 1048576.
+ *
+ * expecto_tfidf_stats writes idf[n] and adds the chunk's row sums into rowsum_acc[m].  No scratch: a
+ * workgroup owns 16 marks, each of its 16 lanes per mark adds the columns y, y+16, ... in ascending
+ * order, and the 16 partial sums are added in ascending y before the one add into rowsum_acc.
+ *
+ * expecto_tfidf_gram: H_acc[m,m] += sum_n t[n,:]^T t[n,:], the full symmetric matrix (both triangles
+ * get the same bits), on v_mfma_f64_16x16x4_f64.  The columns are split into
+ * expecto_tfidf_gram_parts(m, n) contiguous parts; each writes its 64 x 64 upper-triangle tiles to
+ * `workspace` (DEVICE, at least expecto_tfidf_gram_workspace(m, n) bytes, 8-byte aligned), and a
+ * second kernel adds the parts in ascending order into H_acc.  Both sizes are pure host functions
+ * (0 for an empty or refused shape).
+ *
+ * expecto_tfidf_project: out[c, n] = (float)(idf_n * sum_i P[c,i] x[n,i]) for c < k, P float64 [k, m],
+ * out float32 with row stride ld_out >= n; the sum in float64 over i ascending, rounded once.
+ *
+ * expecto_tfidf_transform: X_acc[i, c] += sum_n x[n,i] idf_n V[c,n], V float32 [k, n] with row stride
+ * ld_v >= n, X_acc float64 [m, k]; columns split and reduced as the Gram's, with
+ * expecto_tfidf_transform_parts / _workspace(m, k, n). */
+int expecto_tfidf_stats(const float* D, long long n, long long ld, const int* keep_idx, int m, double* idf,
+                        double* rowsum_acc, void* stream);
+int expecto_tfidf_gram_parts(int m, long long n);
+size_t expecto_tfidf_gram_workspace(int m, long long n);
+int expecto_tfidf_gram(const float* D, long long n, long long ld, const int* keep_idx, int m, const double* idf,
+                       double* H_acc, void* workspace, size_t workspace_bytes, void* stream);
+int expecto_tfidf_project(const float* D, long long n, long long ld, const int* keep_idx, int m, const double* idf,
+                          const double* P, int k, float* out, long long ld_out, void* stream);
+int expecto_tfidf_transform_parts(int m, int k, long long n);
+size_t expecto_tfidf_transform_workspace(int m, int k, long long n);
+int expecto_tfidf_transform(const float* D, long long n, long long ld, const int* keep_idx, int m, const double* idf,
+                            const float* V, long long ld_v, int k, double* X_acc, void* workspace,
+                            size_t workspace_bytes, void* stream);
 
 const char* expecto_last_error(void);
 const char* expecto_version(void);
