@@ -85,6 +85,11 @@ SIGNATURES = {
     "expecto_pairwise_euclidean": (ctypes.c_int, [c_vp, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong,
                                                   c_vp, c_vp]),
     "expecto_ward_linkage": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp, c_vp, c_vp]),
+    "expecto_square_distances": (ctypes.c_int, [c_vp, ctypes.c_longlong, c_vp, c_vp]),
+    "expecto_silhouette_node_sums": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_longlong, c_vp, c_vp, c_vp,
+                                                    ctypes.c_longlong, c_vp, c_vp]),
+    "expecto_silhouette_cuts": (ctypes.c_int, [c_vp, ctypes.c_longlong, ctypes.c_longlong, c_vp, c_vp, c_vp, c_vp,
+                                               c_vp, ctypes.c_longlong, c_vp, c_vp]),
     "expecto_tfidf_stats": (ctypes.c_int, [c_vp, ctypes.c_longlong, ctypes.c_longlong, c_vp, ctypes.c_int, c_vp, c_vp,
                                            c_vp]),
     "expecto_tfidf_gram_parts": (ctypes.c_int, [ctypes.c_int, ctypes.c_longlong]),

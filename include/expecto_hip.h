@@ -40,6 +40,9 @@
  *   expecto_pairwise_euclidean     scipy's pdist under AgglomerativeClustering().fit
  *   expecto_ward_linkage           and its Ward linkage (interpret_features.py:99-120,
  *                                  interpret_features_grouped.py:103-146)
+ *   expecto_square_distances       scipy's squareform of those distances
+ *   expecto_silhouette_node_sums   the per-cluster distance sums of silhouette_samples, once per tree node
+ *   expecto_silhouette_cuts        silhouette_samples of every cut (interpret_features_grouped.py:120-144)
  *   expecto_tfidf_stats / _gram    tf-idf of the mark tracks and its float64 Gram matrix (svd.py:76-85)
  *   expecto_tfidf_project          components_ of the truncated SVD (svd.py:84-85)
  *   expecto_tfidf_transform        svd.transform(tf_idf) (svd_transform.py:80)
@@ -406,6 +409,45 @@ int expecto_pairwise_euclidean(const double* X, long long n, long long d, long l
  * the cluster merge m made) at heights[i] into sizes[i] points.  n < 2, a NaN distance or a point
  * with no finite distance to any other is refused (EXPECTO_EINVAL). */
 int expecto_ward_linkage(double* condensed, int n, int* children, double* heights, int* sizes);
+
+/* Silhouette of the cuts of one tree (interpret_features_grouped.py:120-144: silhouette_score for
+ * every n_clusters), from the distances above.  d(i,j) is expecto_pairwise_euclidean's distance,
+ * d(i,i) = +0.0.  The arithmetic is fixed:
+ *   node sum   S[v,i] = ((+0.0 + d(i,j1)) + d(i,j2)) + ... over the members j1 < j2 < ... of node v in
+ *              the order the list gives them (the caller lists them ascending): one sequential float64
+ *              chain per (v, i), every add rounded -- np.bincount(labels, weights=D[i]) for that
+ *              cluster.  A parent's sum is never formed from its children's.  j == i adds +0.0, which
+ *              changes nothing: no sum is ever -0.0.
+ *   per cut and point, `own` being the cut's node that holds i:
+ *              a = S[own,i] / (|own| - 1);  b = min over the cut's other nodes v of S[v,i] / |v|;
+ *              s = (b - a) / max(a, b);  a NaN s (a singleton's 0/0, or a = b = 0) becomes +0.0.
+ *              Both divisions are IEEE float64 divisions; nothing is contracted or reassociated.
+ * With the members ascending the samples equal sklearn.metrics.silhouette_samples(squareform(pdist(X)),
+ * labels, metric='precomputed') bit for bit; the score of a cut is the caller's mean of its row.
+ * No atomics: two identical calls give identical bits.  2 <= n <= 1048576 everywhere (EXPECTO_EINVAL
+ * otherwise).  Offsets are int64 and are passed twice, in HOST memory (checked here) and in DEVICE
+ * memory (read by the kernel, which clamps them to the array's length).
+ *
+ * expecto_square_distances: condensed [n(n-1)/2] -> square [n, n] (both DEVICE), both triangles and a
+ * +0.0 diagonal: the layout in which every member row is contiguous over the points.
+ *
+ * expecto_silhouette_node_sums: dist is the square matrix (square != 0) or the condensed one
+ * (square == 0); same bits.  Node v's members are members[node_ptr[v] .. node_ptr[v+1]) (DEVICE int32;
+ * an entry outside [0, n) is passed over).  S (DEVICE) float64 [n_nodes, n].  n_nodes = 0 writes nothing
+ * and succeeds.  Refused: node_ptr[0] != 0, decreasing offsets, a node of more than n members.
+ *
+ * expecto_silhouette_cuts: cut c's nodes are active[cut_ptr[c] .. cut_ptr[c+1]) (DEVICE int32 row
+ * indices of S), own [n_cuts, n] (DEVICE int32) the row of S that holds point i in cut c, sizes
+ * (DEVICE int32 [n_nodes]) the member counts.  samples (DEVICE) float64 [n_cuts, n].  A row index
+ * outside [0, n_nodes) is passed over (as `own`: s = +0.0).  n_cuts = 0 writes nothing and succeeds.
+ * Refused: a cut of fewer than 2 or more than n - 1 nodes, cut_ptr[0] != 0, decreasing offsets. */
+int expecto_square_distances(const double* condensed, long long n, double* square, void* stream);
+int expecto_silhouette_node_sums(const double* dist, int square, long long n, const long long* node_ptr_host,
+                                 const long long* node_ptr, const int* members, long long n_nodes, double* S,
+                                 void* stream);
+int expecto_silhouette_cuts(const double* S, long long n, long long n_nodes, const int* sizes,
+                            const long long* cut_ptr_host, const long long* cut_ptr, const int* active, const int* own,
+                            long long n_cuts, double* samples, void* stream);
 
 /* Truncated SVD of the tf-idf mark tracks (svd.py:58-85, svd_transform.py:49-81), by the float64 Gram
  * matrix of the tf-idf rows; its eigenproblem is the caller's (expecto_amd/svd.py, on the host).
