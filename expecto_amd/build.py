@@ -1,6 +1,7 @@
 """Build libexpecto_hip.so in-tree for gfx950 (``python -m expecto_amd.build``)."""
 from __future__ import annotations
 
+import glob
 import os
 import subprocess
 import sys
@@ -22,8 +23,8 @@ def needs_build() -> bool:
     if not os.path.exists(OUT):
         return True
     t = os.path.getmtime(OUT)
-    deps = SOURCES + [os.path.join(HERE, "csrc", h) for h in ("common.h", "gemm_kernel.h", "seg_plan.h", "ward_linkage.h", "tri_tiles.h")] + [
-                      os.path.join(os.path.dirname(HERE), "include", "expecto_hip.h")]
+    deps = SOURCES + glob.glob(os.path.join(HERE, "csrc", "*.h")) + [
+        os.path.join(os.path.dirname(HERE), "include", "expecto_hip.h")]
     return any(os.path.getmtime(d) > t for d in deps)
 
 

@@ -21,17 +21,19 @@
 
 #include <algorithm>
 #include <array>
-#include <cassert>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
 #include <map>
+#include <memory>
 #include <mutex>
 #include <tuple>
 #include <string>
 #include <vector>
 
+#include "beluga_knobs.h"
 #include "common.h"
+#include "event_pairs.h"
 #include "gemm_kernel.h"
 #include "seg_plan.h"
 
@@ -1532,17 +1534,63 @@ constexpr ConvGeo kConv[5] = {
     {480, 640, 120, 113, 113, 0},  // conv5
     {640, 640, 113, 106, 106, 0},  // conv6 -> FC1 reads 106*640 = 67840 contiguous floats
 };
-// FC1 split-K: a fixed number of slabs per handle (default 8 of 8480; a divisor of
-// 67840/32 = 2120 K blocks), whatever the batch, so an FC1 output never depends on how many
-// windows shared the launch.
-constexpr int kFc2SplitsDefault = 7;   // FC2 K = 63 blocks of 32 -> 7 slabs of 9: a 2000-row FC2 fills
-                                        // 728 workgroups instead of 104 (fixed: sums never depend on M)
-constexpr int kFcSplitsDefault = 8;    // round 2 sweep (tools/knob_sweep.py, interleaved): 8 vs 20 slabs
-                                       // +0.6-0.9 % on the 200-window workload, +0.3-1.2 % on configs[1]
-                                       // (4: -0.6 / -3.7 %), with 2.5x less split-K partial traffic
+static_assert(kFc1In / GBK == kFc1KBlocks && kHidLd / GBK == kFc2KBlocks, "beluga_knobs.h restates the FC K blocks");
+
+// Device memory, zero-filled: rows a kernel reads past a layer's valid rows (padded strides, the
+// last window's Toeplitz tail) then hold finite values before any layer wrote them.
+int dev_alloc_zeroed(void** p, size_t bytes) {
+  hipError_t e = hipMalloc(p, bytes);
+  if (e != hipSuccess) {
+    *p = nullptr;
+    set_error(std::string("hipMalloc: ") + hipGetErrorString(e));
+    return EXPECTO_ENOMEM;
+  }
+  e = hipMemset(*p, 0, bytes);
+  if (e == hipSuccess) e = hipStreamSynchronize(nullptr);   // filled before a launch on any stream writes it
+  if (e != hipSuccess) {
+    (void)hipFree(*p);
+    *p = nullptr;
+    set_error(std::string("hipMemset: ") + hipGetErrorString(e));
+    return EXPECTO_EHIP;
+  }
+  return EXPECTO_OK;
+}
+
+// A device buffer of the handle that grows with the largest call (hipFree synchronises, so each is
+// sized once per size): owned here and freed with the handle, counted in the handle's `bytes`,
+// zero-filled whenever it grows.  Empty (null, 0) after any failure.
+template <class T>
+struct DevBuf {
+  T* p = nullptr;
+  size_t cap = 0;   // elements
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() {
+    if (p) (void)hipFree(p);
+  }
+  operator T*() const { return p; }
+  void release(size_t& bytes) {
+    if (p) (void)hipFree(p);
+    bytes -= cap * sizeof(T);
+    p = nullptr;
+    cap = 0;
+  }
+  int reserve(size_t n, size_t& bytes) {
+    if (n <= cap) return EXPECTO_OK;
+    release(bytes);
+    void* q = nullptr;
+    int rc = dev_alloc_zeroed(&q, n * sizeof(T));
+    if (rc) return rc;
+    p = static_cast<T*>(q);
+    cap = n;
+    bytes += n * sizeof(T);
+    return EXPECTO_OK;
+  }
+};
 }  // namespace
 
-struct expecto_beluga {
+struct expecto_beluga : expecto::BelugaKnobs {
   int device = 0;
   int max_batch = 0;
   float* w1 = nullptr;
@@ -1587,89 +1635,60 @@ struct expecto_beluga {
   long long* a_rows = nullptr;  // FC1 row table (segment path), max_batch entries
   long long* c_rows = nullptr;  // FC2 output-row table (segment path), fc2_rows + max_batch entries
   int fc2_rows = 0;             // segment path, FC2 unsplit: h1 rows gathered per FC2 launch
-  int* win_seg_d = nullptr;     // window tables of the current segment call
-  int* alt_w_d = nullptr;       //   segment pairs: windows holding the SNV / the others
-  int* copy_w_d = nullptr;
-  int* seg_var_d = nullptr;     //   segment pairs: SNV index per segment
-  int seg_var_cap = 0;
-  int* win_off_d = nullptr;
-  int* win_row_d = nullptr;
-  int* fc_perm_d = nullptr;      // segment pairs: FC row order of both strands' windows (4 x win_cap)
+  DevBuf<int> win_seg_d;        // window tables of the current segment call (n_win entries)
+  DevBuf<int> alt_w_d;          //   segment pairs: windows holding the SNV / the others (per strand: 2 n_win)
+  DevBuf<int> copy_w_d;
+  DevBuf<int> seg_var_d;        //   segment pairs: SNV index per segment
+  DevBuf<int> win_off_d;
+  DevBuf<int> win_row_d;
+  DevBuf<int> fc_perm_d;        //   segment pairs: FC row order of both strands' windows (FC order, alt order: 4 n_win)
   hipStream_t st2 = nullptr;     // pair path: alt-delta launches overlap the ref launches
   hipEvent_t pev[16] = {};       //   (ordering events, no timing)
-  bool overlap = true;           //   EXPECTO_OVERLAP=0: one stream (same bits either way)
   float* DA = nullptr;           // alt-delta buffers (pair path), lazily allocated:
   float* D0 = nullptr;           //   DA = assembled input patch, D0/D1 = alternating W_l-row runs
   float* D1 = nullptr;
   uint8_t* delta_codes = nullptr;
   int* seg_tab = nullptr;        //   per-segment delta rows (segment pairs)
   float* slab_mask = nullptr;    //   alt FC1 split-K slab mask per M tile (pair path)
-  int win_cap = 0;
   size_t bytes = 0;
   std::vector<void*> allocs;
   int precision = EXPECTO_PRECISION_BF16X6;
-  int fc_splits = kFcSplitsDefault;   // FC1 split-K slabs: a divisor of 2120 K blocks, <= 32
-  int fc2_splits = kFc2SplitsDefault; // FC2 split-K slabs: a divisor of 63 K blocks
-  double fc1_m_order_mb = 80.0;       // FC1 dispatch: M tiles fastest while one split's A is <= this
-  int fc1_order = 3;                  // FC1 dispatch order (EXPECTO_FC1_ORDER): 3 grouped M tiles (default),
-                                      // 0 M-fastest / N-fastest by A-slab size, 2 slab-outermost
-  int fc1_m_group = 8;                // order 3: M tiles per group (EXPECTO_FC1_M_GROUP)
-  bool fc_wide = true;                // f16x3 FC split-K GEMMs on 336-column tiles (EXPECTO_FC_WIDE; same bits)
-  int conv_tile = 0;                  // f16x3 conv M tile: 0 = auto (conv_tile_rows), 256 or 384
-  bool conv_ea = true;                // f16x3 conv consumers' early next-stage reads (EXPECTO_CONV_EA)
-  bool fc_skinny = true;              // FC1 / FC2 of <= 32 rows on 32 x 32 tiles (EXPECTO_FC_SKINNY; same bits)
-  int fc1_narrow = -1;                // grouped FC1 tile width: -1 auto (fc1_narrow), 0 336, 1 112 columns
-  int conv_narrow = -1;               // conv5 / conv6 tile width: -1 auto (conv_narrow), 0 160, 1 64 columns
   bool narrow_scope = false;          // inside forward_chunk: auto narrow tiles allowed (nothing runs beside)
-  int seg_chunk_windows = 0;          // segment path: windows per chunk cap (0 = none; tuning knob)
-  bool seg_merge_strands = true;      // segment path: a chunk may hold entries of both strands (EXPECTO_SEG_MERGE_STRANDS)
   int cus = 0;                        // compute units of the device (workgroups per round)
-  bool pool_one_pass = true;          // segment path: pool2 of all phases in one pass (same bits)
-  bool pool_fused = true;             // segment path, phases {0, 2}: pool2 in conv4's epilogue (EXPECTO_POOL_FUSED; same bits)
-  float* seam = nullptr;              //   its tile-seam rows (4 per 256-row tile) and seg_delta_pool's ref rows
-  float* edge = nullptr;
-  size_t seam_cap = 0, edge_cap = 0;
-  bool fuse_conv1 = true;             // f16x3 codes input: conv1 inside the conv2 launch (EXPECTO_FUSE_CONV1; same bits)
-  bool kmer_on = true;                // f16x3 codes input: conv1 + conv2 + pool1 from the k-mer table (EXPECTO_CONV2_TABLE)
+  DevBuf<float> seam;                 // fused pool2: its tile-seam rows (4 per 256-row tile) and seg_delta_pool's ref rows
+  DevBuf<float> edge;
   float* kmer = nullptr;              //   the table (shared by handles with the same conv1 / conv2 weights)
   uint64_t kmer_key = 0;
-  bool kmer_quad = true;              //   conv2 rows from the quad tables (EXPECTO_KMER_QUAD=0: pair tables only)
   int kmer_state = 1;                 //   0 held, 1 off (EXPECTO_CONV2_TABLE=0), 2 no room (conv2_table_active)
-  bool fk_on = true;                  // f16x3 FC1 as a block-Karatsuba convolution (EXPECTO_FC1_KARATSUBA)
-  int fk_role = 4;                    //   role of per-window forwards (EXPECTO_FC1_ROLE; 4 = direct FC1, the default; 0..3 Karatsuba)
   float* fkw = nullptr;               //   the 9 products' + tail weight planes [npad][kFkKbTotal][2][32] fp16
   int* fk_sw = nullptr;               //   their per-row scale exponents
   float* fk_cs = nullptr;             //   column unscale 2^-(sx[5] + fk_sw[n])
-  float* fk_seq[3] = {};              //   row sequences D1, D2, DD (x's row layout), fk_seq_rows rows each
-  long long fk_seq_rows = 0;
+  DevBuf<float> fk_seq[3];            //   row sequences D1, D2, DD (x's row layout) + a 16-row tail pad
   long long* fk_grows = nullptr;      //   group starts (per product), window starts, partial rows, alt masks
   long long* fk_wrows = nullptr;
   int* fk_prow = nullptr;
   unsigned* fk_mask = nullptr;
-  int fk_slice = 24576;               //   windows per Karatsuba FC1 launch on the segment path (EXPECTO_FC1K_SLICE):
-  float* fk_part = nullptr;           //   its partial rows, FC1 output rows, window / output rows, block residues
+  float* fk_part = nullptr;           //   a segment-path launch's partial rows, FC1 output rows, window / output rows, block residues
   float* fk_h1 = nullptr;
   long long* fk_arows = nullptr;
   long long* fk_crows = nullptr;
   int* fk_gres = nullptr;            //   kGresPerBatch * max_batch entries (a chunk's conv6 blocks)
-  float* fk_aseq[3] = {};             //   segment pairs' in-place alt FC1: the alt blocks' sequences, row groups
-  long long fk_aseq_rows = 0;
+  DevBuf<float> fk_aseq[3];           //   segment pairs' in-place alt FC1: the alt blocks' sequences, row groups
   int* fk_rgrp = nullptr;             //   of the product rows, group / window (block, row), alt windows'
   int* fk_ginfo = nullptr;            //   partial rows and order, masks
   int* fk_winfo = nullptr;
   int* fk_aprow = nullptr;
   int* fk_aperm = nullptr;
   unsigned* fk_smask = nullptr;
-  bool onehot_as_codes = true;        // forward_onehot: exact one-hot input through the k-mer gather (EXPECTO_ONEHOT_CODES)
   uint8_t* oh_codes = nullptr;        //   its codes, max_batch x 2000 (allocated on first use)
   int* oh_bad = nullptr;              //   its check flag
   bool oh_hint_bad = false;           //   the last input was not one-hot: check first instead of a speculative run
   int* hflags = nullptr;              // pinned, device-mapped host words the per-call checks read their flags into
   int* hflags_d = nullptr;            //   their device address (take_flags writes them: no blit kernels per call)
   bool profiling = false;
-  std::vector<hipEvent_t> ev_pool;
+  std::vector<hipEvent_t> ev_pool;           // pair p of `ev`: events 2p (start) and 2p + 1 (stop)
+  EventPairs ev;
   std::vector<std::pair<int, int>> pending;  // (layer, event index of start)
-  size_t ev_next = 0;
   // timing slots 0..8: the layers of every forward; 9..17: the same layers' alt-delta launches
   // (pair / segment-pair paths), kept apart so a slot's launches are those of one kernel shape
   int timer_base = 0;            // kNumLayers while an alt-delta run is being launched
@@ -1689,21 +1708,11 @@ struct expecto_beluga {
 };
 
 namespace {
+// Fixed-size device memory of the handle (zero-filled, counted, freed with it through `allocs`).
 int dalloc(expecto_beluga* h, float** p, size_t nfloat) {
   void* ptr = nullptr;
-  hipError_t e = hipMalloc(&ptr, nfloat * sizeof(float));
-  if (e != hipSuccess) {
-    set_error(std::string("hipMalloc: ") + hipGetErrorString(e));
-    return EXPECTO_ENOMEM;
-  }
-  // zero-filled: rows a kernel reads past a layer's valid rows (padded strides, the last window's
-  // Toeplitz tail) then hold finite values before any layer wrote them
-  e = hipMemset(ptr, 0, nfloat * sizeof(float));
-  if (e != hipSuccess) {
-    (void)hipFree(ptr);
-    set_error(std::string("hipMemset: ") + hipGetErrorString(e));
-    return EXPECTO_EHIP;
-  }
+  int rc = dev_alloc_zeroed(&ptr, nfloat * sizeof(float));
+  if (rc) return rc;
   h->allocs.push_back(ptr);
   h->bytes += nfloat * sizeof(float);
   *p = static_cast<float*>(ptr);
@@ -1743,8 +1752,7 @@ int kmer_no_room(expecto_beluga* h, const char* why) {
 
 int kmer_acquire(expecto_beluga* h, const float* const* params, hipStream_t st) {
   const size_t tb = kKmerFloats * sizeof(float), fb = (size_t)kMer8 * 320 * sizeof(double);
-  if (const char* e = getenv("EXPECTO_KMER_MAX_BYTES"))
-    if ((double)tb > atof(e)) return kmer_no_room(h, "EXPECTO_KMER_MAX_BYTES");
+  if ((double)tb > h->kmer_max_bytes) return kmer_no_room(h, "EXPECTO_KMER_MAX_BYTES");
   std::vector<float> hw(320 * 32 + 320 + 320 * 320 * 8);
   EXPECTO_HIP_CHECK(hipMemcpyAsync(hw.data(), params[0], 320 * 32 * sizeof(float), hipMemcpyDeviceToHost, st));
   EXPECTO_HIP_CHECK(hipMemcpyAsync(hw.data() + 320 * 32, params[1], 320 * sizeof(float), hipMemcpyDeviceToHost, st));
@@ -1803,7 +1811,6 @@ void kmer_release(expecto_beluga* h) {
     if (g_kmer[i].T == h->kmer) {
       auto& hs = g_kmer[i].holders;
       const auto it = std::find(hs.begin(), hs.end(), h);
-      assert(it != hs.end() && "k-mer table held by an unregistered handle");
       if (it != hs.end()) hs.erase(it);   // (never erase end(): a handle not in the list is left alone)
       if (hs.empty()) {
         (void)hipFree(g_kmer[i].T);
@@ -1899,47 +1906,46 @@ int resolve_events(expecto_beluga* h) {
     a[2] += r.macs;
   }
   h->pending_launch.clear();
-  h->ev_next = 0;
+  h->ev.reset();
   return EXPECTO_OK;
 }
 
-// Times ONE GEMM launch (its own event pair, beside the layer slot's) for the per-launch log.
-struct LaunchTimer {
+int grow_event_pool(expecto_beluga* h, size_t pairs) {
+  for (size_t i = 0; i < 2 * pairs; ++i) {
+    hipEvent_t e;
+    EXPECTO_HIP_CHECK(hipEventCreate(&e));
+    h->ev_pool.push_back(e);
+  }
+  h->ev.grow(pairs);
+  return EXPECTO_OK;
+}
+
+// Times the launches of its scope on stream s with one event pair (event_pairs.h), while profiling:
+// a sample of the layer's slot or, given rows (and macs), ONE GEMM launch for the per-launch log,
+// beside the layer slot's own timer.  A timer that gets no pair records nothing.
+struct Timer {
   expecto_beluga* h;
-  int idx = -1;
   hipStream_t st;
   expecto_beluga::LaunchRec rec;
-  LaunchTimer(expecto_beluga* hh, int layer, long long rows, double macs, hipStream_t s) : h(hh), st(s) {
+  Timer(expecto_beluga* hh, int layer, hipStream_t s, long long rows = -1, double macs = 0.0)
+      : h(hh), st(s), rec{hh->timer_base + layer, rows, -1, macs} {
     if (!h->profiling) return;
-    if (h->ev_next + 2 > h->ev_pool.size()) resolve_events(h);
-    idx = (int)h->ev_next;
-    h->ev_next += 2;
-    rec = {h->timer_base + layer, rows, idx, macs};
-    (void)hipEventRecord(h->ev_pool[idx], st);
+    const EventPairs::Room room = h->ev.room();
+    if (room == EventPairs::Room::kResolve) (void)resolve_events(h);   // no timer is open: read and reset the pool
+    if (room == EventPairs::Room::kGrow && grow_event_pool(h, 1)) return;
+    const int pair = h->ev.open();
+    if (pair < 0) return;
+    rec.idx = 2 * pair;
+    (void)hipEventRecord(h->ev_pool[rec.idx], st);
   }
-  ~LaunchTimer() {
-    if (idx < 0) return;
-    (void)hipEventRecord(h->ev_pool[idx + 1], st);
-    h->pending_launch.push_back(rec);
-  }
-};
-
-struct LayerTimer {
-  expecto_beluga* h;
-  int layer;
-  int idx = -1;
-  hipStream_t st;
-  LayerTimer(expecto_beluga* hh, int l, hipStream_t s) : h(hh), layer(hh->timer_base + l), st(s) {
-    if (!h->profiling) return;
-    if (h->ev_next + 2 > h->ev_pool.size()) resolve_events(h);
-    idx = (int)h->ev_next;
-    h->ev_next += 2;
-    (void)hipEventRecord(h->ev_pool[idx], st);
-  }
-  ~LayerTimer() {
-    if (idx < 0) return;
-    (void)hipEventRecord(h->ev_pool[idx + 1], st);
-    h->pending.push_back({layer, idx});
+  ~Timer() {
+    if (rec.idx < 0) return;
+    (void)hipEventRecord(h->ev_pool[rec.idx + 1], st);
+    h->ev.close();
+    if (rec.rows < 0)
+      h->pending.push_back({rec.layer, rec.idx});
+    else
+      h->pending_launch.push_back(rec);
   }
 };
 
@@ -2098,7 +2104,7 @@ int launch_gemm(const GemmArgs& a, int splits, hipStream_t st, int bm = 0) {
 
 int run_conv1(expecto_beluga* h, const float* x, const uint8_t* codes, long long code_stride, int n_src, int mode,
               long long row0, int nb, int len, int out_rows, hipStream_t st, float* dst = nullptr) {
-  LayerTimer lt(h, 0, st);
+  Timer lt(h, 0, st);
   if (h->profiling) h->macs[h->timer_base + 0] += (double)nb * (len - 7) * 320 * 32;
   if (g_precision == EXPECTO_PRECISION_F16X3 && h->w1h) {
     dim3 grid((len - 7 + C1H_ROWS - 1) / C1H_ROWS, nb);
@@ -2137,7 +2143,7 @@ bool use_kmer(const expecto_beluga* h, const float* x) {
 }
 
 int run_conv2_kmer(expecto_beluga* h, const C1Src& f, long long n_win, int rows, int s_out, float* dst, hipStream_t st) {
-  LayerTimer lt(h, 1, st);
+  Timer lt(h, 1, st);
   const int rb = (rows + KP_ROWS - 1) / KP_ROWS;
   const long long nblk = n_win * rb;
   EXPECTO_REQUIRE(nblk > 0 && nblk < (1LL << 31) && f.len >= 18, "conv2 k-mer grid / window length");
@@ -2199,9 +2205,9 @@ int run_conv(expecto_beluga* h, int l, const float* src, float* dst, long long g
     // conv1's algorithmic MACs stay in conv1's slot (its time is inside this launch)
     if (h->profiling) h->macs[h->timer_base + 0] += (double)groups * (f1->len - 7) * 320 * 32;
   }
-  LayerTimer lt(h, l + 1, st);
+  Timer lt(h, l + 1, st);
   if (h->profiling) h->macs[h->timer_base + l + 1] += (double)a.M * g.cout * a.kper;
-  LaunchTimer lrec(h, l + 1, a.M, (double)a.M * g.cout * a.kper, st);
+  Timer lrec(h, l + 1, st, a.M, (double)a.M * g.cout * a.kper);
   if (pool) {
     EXPECTO_REQUIRE(s_in % 4 == 0, "pool epilogue needs 4-aligned row groups");
     return l == 0 ? launch_gemm<2, EPI_RELU_POOL4>(a, 1, st, bm) : launch_gemm<4, EPI_RELU_POOL4>(a, 1, st, bm);
@@ -2252,20 +2258,8 @@ int run_conv4_pool_fused(expecto_beluga* h, const float* src, float* dst, long l
   EXPECTO_REQUIRE(g_precision == EXPECTO_PRECISION_F16X3 && s_in % 4 == 0 && t4 <= s_in && a.n_tiles == 3,
                   "fused conv4 + pool2: f16x3 segment blocks at a 4-aligned row stride");
   const size_t seam_rows = (size_t)a.m_tiles * 4, edge_rows = tab ? (size_t)groups * kSegEdge : 0;
-  auto grow = [&](float*& b, size_t& cap, size_t rows) -> int {   // (grown once per handle and size)
-    if (rows <= cap) return EXPECTO_OK;
-    if (b) EXPECTO_HIP_CHECK(hipFree(b));
-    b = nullptr;
-    h->bytes -= cap * 480 * 4;
-    cap = 0;
-    EXPECTO_HIP_CHECK(hipMalloc(&b, rows * 480 * 4));
-    EXPECTO_HIP_CHECK(hipMemset(b, 0, rows * 480 * 4));
-    cap = rows;
-    h->bytes += rows * 480 * 4;
-    return EXPECTO_OK;
-  };
   int rc;
-  if ((rc = grow(h->seam, h->seam_cap, seam_rows)) || (rc = grow(h->edge, h->edge_cap, edge_rows))) return rc;
+  if ((rc = h->seam.reserve(seam_rows * 480, h->bytes)) || (rc = h->edge.reserve(edge_rows * 480, h->bytes))) return rc;
   a.c_seam = h->seam;
   a.c_edge = h->edge;
   a.unp_tab = tab;
@@ -2274,16 +2268,16 @@ int run_conv4_pool_fused(expecto_beluga* h, const float* src, float* dst, long l
   const long long nblk = a.m_tiles * a.n_tiles;
   EXPECTO_REQUIRE(nblk > 0 && nblk < (1LL << 31), "gemm grid out of range");
   {
-    LayerTimer lt(h, 3, st);
+    Timer lt(h, 3, st);
     if (h->profiling) h->macs[h->timer_base + 3] += (double)a.M * g.cout * a.kper;
-    LaunchTimer lrec(h, 3, a.M, (double)a.M * g.cout * a.kper, st);
+    Timer lrec(h, 3, st, a.M, (double)a.M * g.cout * a.kper);
     if (g_conv_ea)
       beluga_conv_h3p<4, EPI_POOL_PH02, 256 | 64, 4><<<dim3((unsigned)nblk), dim3(512), 0, st>>>(a);
     else
       beluga_conv_h3p<4, EPI_POOL_PH02, 256, 4><<<dim3((unsigned)nblk), dim3(512), 0, st>>>(a);
     if ((rc = check_launch("beluga_conv_h3p pool2"))) return rc;
   }
-  LayerTimer lt(h, 3, st);   // pool2 is timed with conv4
+  Timer lt(h, 3, st);   // pool2 is timed with conv4
   if (a.m_tiles > 1)
     pool2_tile_seams<<<dim3((unsigned)(a.m_tiles - 1)), dim3(64), 0, st>>>(h->seam, a.M, s_in, t4, s5, dst);
   return check_launch("pool2_tile_seams");
@@ -2352,7 +2346,7 @@ int run_fc1(expecto_beluga* h, const float* act, const long long* a_rows, int nb
       a.m_fastest = 0;
       a.linear_order = 0;
       a.n_tile_cols = FCW_BN;
-      if (!ks_mask && fc_skinny(h, nb)) {   // <= 32 rows: 48 columns, deep ring
+      if (!ks_mask && fc_skinny(h, nb)) {   // <= 32 rows: 32 columns, 9-stage ring
         a.n_tile_cols = 16 * FCS_NB;
         a.n_tiles = kHidLd / a.n_tile_cols;
       } else if (!ks_mask && fc1_narrow(h, m_tiles * splits)) {   // small per-window batches: 112 columns
@@ -2366,12 +2360,12 @@ int run_fc1(expecto_beluga* h, const float* act, const long long* a_rows, int nb
     a.split_stride = part_rows * kHidLd;
     a.ks_mask = ks_mask;
     EXPECTO_REQUIRE(!ks_mask || planes_gemm(), "slab mask needs the planes GEMM");
-    LayerTimer lt(h, 6, st);
+    Timer lt(h, 6, st);
     if (h->profiling) h->macs[h->timer_base + 6] += (double)nb * kFc1Out * kFc1In * slab_frac;
     if ((rc = launch_gemm<7, EPI_PARTIAL>(a, splits, st))) return rc;
   }
   {
-    LayerTimer lt(h, 7, st);
+    Timer lt(h, 7, st);
     const long long count = (long long)nb * kHidLd;
     const bool f16 = g_precision == EXPECTO_PRECISION_F16X3;
     if (act_fmt() == 2)
@@ -2410,7 +2404,7 @@ int run_fc2(expecto_beluga* h, const float* h1, int nb, float* y, hipStream_t st
     if (wide) {
       a.m_fastest = 0;
       a.n_tile_cols = FCW_BN;
-      if (fc_skinny(h, nb)) {   // <= 32 rows: 48 columns, deep ring
+      if (fc_skinny(h, nb)) {   // <= 32 rows: 32 columns, 9-stage ring
         a.n_tile_cols = 16 * FCS_NB;
         a.n_tiles = (kNFeat + a.n_tile_cols - 1) / a.n_tile_cols;
       } else if (fc1_narrow(h, m_tiles * h->fc2_splits)) {   // small per-window batches: 112 columns
@@ -2422,7 +2416,7 @@ int run_fc2(expecto_beluga* h, const float* h1, int nb, float* y, hipStream_t st
     a.ldc = kHidLd;
     a.n_store = kNFeat;
     a.split_stride = (long long)nb * kHidLd;
-    LayerTimer lt(h, 8, st);
+    Timer lt(h, 8, st);
     if (h->profiling) h->macs[h->timer_base + 8] += (double)nb * kNFeat * kFc1Out;
     if (h->fc2_splits == 1) {
       // no split: bias + sigmoid in the GEMM epilogue, rows scattered through c_rows (the
@@ -2512,29 +2506,12 @@ int fk_seg_buffers(expecto_beluga* h) {
   return EXPECTO_OK;
 }
 
-// The D1 / D2 / DD sequence buffers for `rows` conv6 rows (grown on demand; hipFree synchronises,
-// so they are sized once for the largest call).
+// The D1 / D2 / DD sequence buffers for `rows` conv6 rows (+ the 16-row Toeplitz over-read pad)
 int fk_seq_alloc(expecto_beluga* h, long long rows, int set = 0) {
-  float** b = set ? h->fk_aseq : h->fk_seq;
-  long long& cap = set ? h->fk_aseq_rows : h->fk_seq_rows;
-  if (rows <= cap && b[0]) return EXPECTO_OK;
-  for (int i = 0; i < 3; ++i)
-    if (b[i]) {
-      EXPECTO_HIP_CHECK(hipFree(b[i]));
-      b[i] = nullptr;
-    }
-  h->bytes -= (size_t)cap * 640 * 4 * 3;
-  cap = 0;
-  for (int i = 0; i < 3; ++i) {
-    hipError_t e = hipMalloc(&b[i], (size_t)rows * 640 * 4 + 16 * 640 * 4);
-    if (e != hipSuccess) {
-      set_error(std::string("hipMalloc (FC1 sequences): ") + hipGetErrorString(e));
-      return EXPECTO_ENOMEM;
-    }
-  }
-  cap = rows;
-  h->bytes += (size_t)rows * 640 * 4 * 3;
-  return EXPECTO_OK;
+  int rc = EXPECTO_OK;
+  for (DevBuf<float>& b : set ? h->fk_aseq : h->fk_seq)
+    if ((rc = b.reserve(((size_t)rows + 16) * 640, h->bytes))) break;
+  return rc;
 }
 
 // D1 / D2 / DD of `blocks` blocks of T conv6 rows at a stride of s rows (tab: alt blocks, see fk_seq_h2)
@@ -2542,8 +2519,8 @@ int fk_sequences(expecto_beluga* h, const float* x, long long blocks, int T, int
                  hipStream_t st, const int* gres = nullptr, int set = 0) {
   int rc;
   if ((rc = fk_seq_alloc(h, blocks * s, set))) return rc;
-  float* const* out = set ? h->fk_aseq : h->fk_seq;
-  LayerTimer lt(h, 7, st);   // the sequences are timed with the FC1 reduction (slot fc1_reduce)
+  const DevBuf<float>* out = set ? h->fk_aseq : h->fk_seq;
+  Timer lt(h, 7, st);   // the sequences are timed with the FC1 reduction (slot fc1_reduce)
   const long long nblk = blocks * 7;   // 7 workgroups of 4 residue walks per block
   EXPECTO_REQUIRE(nblk > 0 && nblk < (1LL << 31), "FC1 sequence grid");
   fk_seq_h2<<<dim3((unsigned)nblk), dim3(320), 0, st>>>(x, T, s, tab, n_ph, gres, out[0], out[1], out[2], h->ovf);
@@ -2560,7 +2537,7 @@ struct FkProducts {
 
 // FC1 output rows of n windows from their kFkParts partial rows each (prow), fk_reduce_h2
 int fk_reduce(expecto_beluga* h, const float* part, const int* prow, int n, float* h1, hipStream_t st) {
-  LayerTimer lt(h, 7, st);
+  Timer lt(h, 7, st);
   const long long count4 = (long long)n * (kHidLd / 4);
   fk_reduce_h2<<<dim3((unsigned)((count4 + 255) / 256)), dim3(256), 0, st>>>(part, prow, count4, h->fc1b, h1, h->fk_cs,
                                                                            exp2i(h->sx[6]), h->ovf);
@@ -2598,7 +2575,7 @@ bool fc_skinny(const expecto_beluga* h, long long rows) {
 // of `part` in that order (the layout prow was built for); then fk_reduce_h2 into h1.  x: conv6 rows
 // (the product X@3 and the tail), seq: their D1 / D2 / DD.  mask (alt, in place): descriptor d runs
 // only the M tiles with bit 0 of mask[d * tiles + tile] set.
-int fk_fc1(expecto_beluga* h, const float* x, float* const* seq, const FkProducts& pr, const long long* w_rows, int n,
+int fk_fc1(expecto_beluga* h, const float* x, const DevBuf<float>* seq, const FkProducts& pr, const long long* w_rows, int n,
            const int* prow, float* h1, hipStream_t st, const unsigned* mask = nullptr, int tiles = 0,
            float* part = nullptr, long long part_cap = 0) {
   if (!part) {
@@ -2637,7 +2614,7 @@ int fk_fc1(expecto_beluga* h, const float* x, float* const* seq, const FkProduct
     const int lay = pr.lay[g] ? pr.lay[g] : pr.cnt[g];
     for (int s = 0; lay > 0 && s < kFkSlabs; ++s) {
       if (pr.cnt[g] > 0)
-        add(kFkSeq[g] ? seq[kFkSeq[g] - 1] : x, pr.g_rows + pr.off[g], 25LL * kFkBlk[g] * 640 + (long long)s * kFkK / kFkSlabs,
+        add(kFkSeq[g] ? seq[kFkSeq[g] - 1].p : x, pr.g_rows + pr.off[g], 25LL * kFkBlk[g] * 640 + (long long)s * kFkK / kFkSlabs,
             g * kFkKb + s * kFkKb / kFkSlabs, kFkKb / kFkSlabs, pr.cnt[g], lay);
       else {
         row += lay;   // (in-place alt launch: no alt group needs this product; keep the ref layout)
@@ -2649,7 +2626,7 @@ int fk_fc1(expecto_beluga* h, const float* x, float* const* seq, const FkProduct
   EXPECTO_REQUIRE(G.n <= FCK_MAX && blk < (1LL << 31), "Karatsuba FC1 descriptors");
   EXPECTO_REQUIRE(row <= part_cap, "Karatsuba FC1 partial rows");
   {
-    LayerTimer lt(h, 6, st);
+    Timer lt(h, 6, st);
     if (h->profiling) {
       if (!mask) {
         h->macs[h->timer_base + 6] += macs;
@@ -3031,7 +3008,7 @@ int seg_trunk(const SegCall& c, const SegChunk& ck, PQSwap& pq) {
   if (pr && ((rc = seg_st_wait(c, h->pev[6])) || (rc = seg_alt_gemm(c, ck, 2, 1, kA4u, kW4u, false, h->D1))))
     return rc;
   if (!pfused) {  // pool2 phases (Q -> P)
-    LayerTimer lt(h, 3, st);
+    Timer lt(h, 3, st);
     if (act_fmt() == 2 && h->pool_one_pass) {   // all phases in one pass over the conv4 rows
       dim3 grid((g.S5 + 3) / 4, ns);
       pool4_phases_h2m<<<grid, dim3(256), 0, st>>>(h->Q, g.T4, g.T4, 480, n_ph, c.ph4, g.S5, h->P);
@@ -3267,24 +3244,12 @@ int forward_segments(expecto_beluga* h, const uint8_t* codes, int n_seg, int L, 
   }
   int rc;
   if (pr && (rc = ensure_delta(h))) return rc;
-  if (n_win > h->win_cap) {
-    for (int** b : {&h->win_seg_d, &h->win_off_d, &h->win_row_d, &h->alt_w_d, &h->copy_w_d, &h->fc_perm_d}) {
-      if (*b) EXPECTO_HIP_CHECK(hipFree(*b));
-      *b = nullptr;
-    }
-    h->win_cap = 0;
-    for (int** b : {&h->win_seg_d, &h->win_off_d, &h->win_row_d}) EXPECTO_HIP_CHECK(hipMalloc(b, n_win * sizeof(int)));
-    for (int** b : {&h->alt_w_d, &h->copy_w_d}) EXPECTO_HIP_CHECK(hipMalloc(b, 2 * n_win * sizeof(int)));   // per strand
-    EXPECTO_HIP_CHECK(hipMalloc(&h->fc_perm_d, 4 * n_win * sizeof(int)));   // per strand: FC order, alt order
-    h->win_cap = n_win;
-  }
-  if (pr && n_seg > h->seg_var_cap) {
-    if (h->seg_var_d) EXPECTO_HIP_CHECK(hipFree(h->seg_var_d));
-    h->seg_var_d = nullptr;
-    h->seg_var_cap = 0;
-    EXPECTO_HIP_CHECK(hipMalloc(&h->seg_var_d, n_seg * sizeof(int)));
-    h->seg_var_cap = n_seg;
-  }
+  const size_t nw = (size_t)n_win;
+  if ((rc = h->win_seg_d.reserve(nw, h->bytes)) || (rc = h->win_off_d.reserve(nw, h->bytes)) ||
+      (rc = h->win_row_d.reserve(nw, h->bytes)) || (rc = h->alt_w_d.reserve(2 * nw, h->bytes)) ||
+      (rc = h->copy_w_d.reserve(2 * nw, h->bytes)) || (rc = h->fc_perm_d.reserve(4 * nw, h->bytes)) ||
+      (pr && (rc = h->seg_var_d.reserve((size_t)n_seg, h->bytes))))
+    return rc;
   // the tables are caller-owned (and local) host memory: stage them through pinned memory
   std::vector<HostCopy> copies;
   if (pr) {
@@ -3580,6 +3545,17 @@ __global__ void take_flags(const int* __restrict__ ovf, int* __restrict__ bad, i
   }
 }
 
+// The f16x3 overflow fallback: clear the flag, count a fallback, rerun fn in bf16x6, restore f16x3.
+template <class F>
+int rerun_bf16x6(expecto_beluga* h, hipStream_t st, F&& fn) {
+  EXPECTO_HIP_CHECK(hipMemsetAsync(h->ovf, 0, sizeof(int), st));
+  h->fallbacks += 1;
+  h->precision = EXPECTO_PRECISION_BF16X6;
+  const int rc = fn();
+  h->precision = EXPECTO_PRECISION_F16X3;
+  return rc;
+}
+
 template <class F>
 int run_checked(expecto_beluga* h, hipStream_t st, F&& fn) {
   if (h->precision != EXPECTO_PRECISION_F16X3 || h->ovf_deferred) return fn();
@@ -3589,13 +3565,7 @@ int run_checked(expecto_beluga* h, hipStream_t st, F&& fn) {
   take_flags<<<1, 64, 0, st>>>(h->ovf, nullptr, h->hflags_d);
   EXPECTO_HIP_CHECK(hipGetLastError());
   EXPECTO_HIP_CHECK(hipStreamSynchronize(st));
-  if (!*flag) return EXPECTO_OK;
-  EXPECTO_HIP_CHECK(hipMemsetAsync(h->ovf, 0, sizeof(int), st));
-  h->fallbacks += 1;
-  h->precision = EXPECTO_PRECISION_BF16X6;
-  rc = fn();
-  h->precision = EXPECTO_PRECISION_F16X3;
-  return rc;
+  return *flag ? rerun_bf16x6(h, st, fn) : (int)EXPECTO_OK;
 }
 }  // namespace
 
@@ -3606,22 +3576,27 @@ int expecto_beluga_create(int device, const float* const* params, int max_batch,
   EXPECTO_REQUIRE(out != nullptr && params != nullptr, "null argument");
   EXPECTO_REQUIRE(max_batch > 0 && max_batch <= (1 << 16), "max_batch out of range");
   for (int i = 0; i < EXPECTO_BELUGA_NPARAMS; ++i) EXPECTO_REQUIRE(params[i] != nullptr, "null parameter pointer");
+  BelugaKnobs knobs;   // read before anything is allocated
+  const char* refusal = beluga_knobs_parse(knobs, getenv);
+  EXPECTO_REQUIRE(refusal == nullptr, refusal);
   EXPECTO_HIP_CHECK(hipSetDevice(device));
   hipStream_t st = as_stream(stream);
-  auto* h = new expecto_beluga();
+  // the guard destroys the handle, with everything it owns so far, on every early return
+  struct Destroy {
+    void operator()(expecto_beluga* p) const { expecto_beluga_destroy(p); }
+  };
+  std::unique_ptr<expecto_beluga, Destroy> guard(new expecto_beluga());
+  expecto_beluga* h = guard.get();
+  static_cast<BelugaKnobs&>(*h) = knobs;
   h->device = device;
   h->max_batch = max_batch;
   if (hipDeviceGetAttribute(&h->cus, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) h->cus = 0;
   int rc = 0;
-  auto fail = [&](int code) {
-    expecto_beluga_destroy(h);
-    return code;
-  };
-  if ((rc = dalloc(h, &h->w1, 320 * 32)) || (rc = dalloc(h, &h->b1, 320))) return fail(rc);
+  if ((rc = dalloc(h, &h->w1, 320 * 32)) || (rc = dalloc(h, &h->b1, 320))) return rc;
   if (hipHostMalloc(&h->hflags, 4 * sizeof(int), hipHostMallocMapped) != hipSuccess ||
       hipHostGetDevicePointer(reinterpret_cast<void**>(&h->hflags_d), h->hflags, 0) != hipSuccess) {
     set_error("hipHostMalloc (flag words)");
-    return fail(EXPECTO_ENOMEM);
+    return EXPECTO_ENOMEM;
   }
   EXPECTO_HIP_CHECK(hipMemcpyAsync(h->w1, params[0], 320 * 32 * sizeof(float), hipMemcpyDeviceToDevice, st));
   EXPECTO_HIP_CHECK(hipMemcpyAsync(h->b1, params[1], 320 * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -3629,17 +3604,17 @@ int expecto_beluga_create(int device, const float* const* params, int max_batch,
     const ConvGeo& g = kConv[l];
     const int np = npad_of(g.cout);
     const long long K = 8LL * g.cin;
-    if ((rc = dalloc(h, &h->wt[l], (size_t)np * K)) || (rc = dalloc(h, &h->bt[l], np))) return fail(rc);
+    if ((rc = dalloc(h, &h->wt[l], (size_t)np * K)) || (rc = dalloc(h, &h->bt[l], np))) return rc;
     const long long tot = np * K;
     repack_conv<<<dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st>>>(params[2 + 2 * l], g.cout, g.cin, np,
                                                                           h->wt[l]);
     pad_copy<<<dim3((np + 255) / 256), dim3(256), 0, st>>>(params[3 + 2 * l], g.cout, np, h->bt[l]);
-    if ((rc = make_planes(h, h->wt[l], np, K, &h->wp[l], st))) return fail(rc);
+    if ((rc = make_planes(h, h->wt[l], np, K, &h->wp[l], st))) return rc;
   }
   const int np1 = npad_of(kFc1Out), np2 = npad_of(kNFeat);
   if ((rc = dalloc(h, &h->fc1w, (size_t)np1 * kFc1In)) || (rc = dalloc(h, &h->fc1b, np1)) ||
       (rc = dalloc(h, &h->fc2w, (size_t)np2 * kHidLd)) || (rc = dalloc(h, &h->fc2b, np2)))
-    return fail(rc);
+    return rc;
   {
     const long long tot = (long long)np1 * kFc1In;
     repack_fc1<<<dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, st>>>(params[12], np1, h->fc1w);
@@ -3649,106 +3624,44 @@ int expecto_beluga_create(int device, const float* const* params, int max_batch,
     pad_copy<<<dim3((np2 + 255) / 256), dim3(256), 0, st>>>(params[15], kNFeat, np2, h->fc2b);
     if ((rc = make_planes(h, h->fc1w, np1, kFc1In, &h->fc1p, st)) ||
         (rc = make_planes(h, h->fc2w, np2, kHidLd, &h->fc2p, st)))
-      return fail(rc);
+      return rc;
   }
-  if ((rc = check_launch("repack"))) return fail(rc);
+  if ((rc = check_launch("repack"))) return rc;
   const size_t pf = p_floats(max_batch), qf = q_floats(max_batch);
-  if (const char* e = getenv("EXPECTO_FC1_SPLITS")) {   // tuning knob (fixed per handle: sums never
-    const int v = atoi(e);                               // depend on the batch)
-    EXPECTO_REQUIRE(v >= 1 && v <= 32 && (kFc1In / GBK) % v == 0, "EXPECTO_FC1_SPLITS must divide 2120 and be <= 32");
-    h->fc_splits = v;
-  }
-  if (const char* e = getenv("EXPECTO_FC2_SPLITS")) {   // tuning knob (fixed per handle, like FC1's)
-    const int v = atoi(e);
-    EXPECTO_REQUIRE(v >= 1 && 63 % v == 0, "EXPECTO_FC2_SPLITS must divide 63");
-    h->fc2_splits = v;
-  }
-  if (const char* e = getenv("EXPECTO_FC1_M_ORDER_MB")) h->fc1_m_order_mb = atof(e);   // same bits either way
-  if (const char* e = getenv("EXPECTO_FC1_ORDER")) h->fc1_order = atoi(e);              // same bits either way
-  if (const char* e = getenv("EXPECTO_FC1_M_GROUP")) h->fc1_m_group = std::max(1, atoi(e));   // same bits
-  if (const char* e = getenv("EXPECTO_FC_WIDE")) h->fc_wide = atoi(e) != 0;                   // same bits
-  if (const char* e = getenv("EXPECTO_OVERLAP")) h->overlap = atoi(e) != 0;   // same bits either way
-  if (const char* e = getenv("EXPECTO_POOL_ONE_PASS")) h->pool_one_pass = atoi(e) != 0;   // same bits either way
-  if (const char* e = getenv("EXPECTO_POOL_FUSED")) h->pool_fused = atoi(e) != 0;         // same bits either way
-  if (const char* e = getenv("EXPECTO_FUSE_CONV1")) h->fuse_conv1 = atoi(e) != 0;         // same bits either way
-  if (const char* e = getenv("EXPECTO_CONV2_TABLE")) h->kmer_on = atoi(e) != 0;   // conv2 on the MFMAs (parity, not bits)
-  if (const char* e = getenv("EXPECTO_KMER_QUAD")) h->kmer_quad = atoi(e) != 0;    // pair tables only (parity, not bits)
-  if (const char* e = getenv("EXPECTO_ONEHOT_CODES")) h->onehot_as_codes = atoi(e) != 0;   // parity, not bits
-  if (const char* e = getenv("EXPECTO_FC1_KARATSUBA")) h->fk_on = atoi(e) != 0;       // parity, not bits
-  if (const char* e = getenv("EXPECTO_FC1K_SLICE")) h->fk_slice = std::max(1, atoi(e));  // same bits either way
-  if (const char* e = getenv("EXPECTO_FC1_ROLE")) {    // per-window forwards' Karatsuba role (tests)
-    const int v = atoi(e);
-    EXPECTO_REQUIRE(v >= 0 && v <= 4, "EXPECTO_FC1_ROLE must be 0..4");
-    h->fk_role = v;
-  }
-  if (const char* e = getenv("EXPECTO_SEG_CHUNK_WINDOWS")) h->seg_chunk_windows = atoi(e);   // same bits either way
-  if (const char* e = getenv("EXPECTO_SEG_MERGE_STRANDS")) h->seg_merge_strands = atoi(e) != 0;   // same bits either way
-  if (const char* e = getenv("EXPECTO_CONV_NARROW")) {   // conv5 / conv6 tile width (same bits either way)
-    const int v = atoi(e);
-    EXPECTO_REQUIRE(v >= -1 && v <= 1, "EXPECTO_CONV_NARROW must be -1 (auto), 0 or 1");
-    h->conv_narrow = v;
-  }
-  if (const char* e = getenv("EXPECTO_FC1_NARROW")) {   // grouped FC1 tile width (same bits either way)
-    const int v = atoi(e);
-    EXPECTO_REQUIRE(v >= -1 && v <= 1, "EXPECTO_FC1_NARROW must be -1 (auto), 0 or 1");
-    h->fc1_narrow = v;
-  }
-  if (const char* e = getenv("EXPECTO_CONV_EA")) h->conv_ea = atoi(e) != 0;   // same bits either way
-  if (const char* e = getenv("EXPECTO_FC_SKINNY")) h->fc_skinny = atoi(e) != 0;   // same bits either way
-  if (const char* e = getenv("EXPECTO_CONV_TILE")) {    // tuning knob: f16x3 conv M tile (same bits)
-    const int v = atoi(e);
-    EXPECTO_REQUIRE(v == 0 || v == 256 || v == 384, "EXPECTO_CONV_TILE must be 0 (auto), 256 or 384");
-    h->conv_tile = v;
-  }
   // segment path with FC2 unsplit: the FC1 slices' h1 rows of a chunk are gathered into one FC2
   // launch of up to fc2_rows rows (a 2,016-deep GEMM fills whole rounds of the chip only at
   // ~20 k rows; EXPECTO_FC2_ROWS, same bits for any value)
-  h->fc2_rows = h->fc2_splits == 1 ? 4 * max_batch : max_batch;
-  if (const char* e = getenv("EXPECTO_FC2_ROWS"))
-    if (h->fc2_splits == 1) h->fc2_rows = std::max(max_batch, atoi(e));
+  h->fc2_rows = h->fc2_splits != 1 ? max_batch : h->fc2_rows_env ? std::max(max_batch, h->fc2_rows_env) : 4 * max_batch;
   // split-K partial rows: FC1's slabs, or the Karatsuba FC1's <= kFkParts partial rows per window
   const size_t partf = (size_t)std::max(h->fc_splits, kFkParts) * max_batch * kHidLd;
   const size_t h1_rows = (size_t)h->fc2_rows + (h->fc2_splits == 1 ? max_batch : 0);
   if ((rc = dalloc(h, &h->P, act_alloc(pf))) || (rc = dalloc(h, &h->Q, act_alloc(qf))) ||
       (rc = dalloc(h, &h->part, partf)) || (rc = dalloc(h, &h->h1, act_alloc(h1_rows * kHidLd))) ||
       (rc = dalloc(h, &h->part2, (size_t)h->fc2_splits * max_batch * kHidLd)))
-    return fail(rc);
+    return rc;
   {
     float* rows = nullptr;
-    if ((rc = dalloc(h, &rows, (size_t)(max_batch + h1_rows) * 2))) return fail(rc);
+    if ((rc = dalloc(h, &rows, (size_t)(max_batch + h1_rows) * 2))) return rc;
     h->a_rows = reinterpret_cast<long long*>(rows);
     h->c_rows = h->a_rows + max_batch;
     float* gr = nullptr;
-    if ((rc = dalloc(h, &gr, (size_t)kGresPerBatch * max_batch))) return fail(rc);
+    if ((rc = dalloc(h, &gr, (size_t)kGresPerBatch * max_batch))) return rc;
     h->fk_gres = reinterpret_cast<int*>(gr);
   }
   EXPECTO_HIP_CHECK(hipMemsetAsync(h->P, 0, act_alloc(pf) * sizeof(float), st));
   EXPECTO_HIP_CHECK(hipMemsetAsync(h->Q, 0, act_alloc(qf) * sizeof(float), st));
   // default arithmetic: f16x3 (fp16 weight planes + activation-scale calibration now)
-  if ((rc = f16_prepare(h, st))) return fail(rc);
-  if (h->kmer_on && (rc = kmer_acquire(h, params, st))) return fail(rc);
+  if ((rc = f16_prepare(h, st))) return rc;
+  if (h->kmer_on && (rc = kmer_acquire(h, params, st))) return rc;
   h->precision = EXPECTO_PRECISION_F16X3;
   EXPECTO_HIP_CHECK(hipStreamSynchronize(st));
-  *out = h;
+  *out = guard.release();
   return EXPECTO_OK;
 }
 
 void expecto_beluga_destroy(expecto_beluga_t h) {
   if (!h) return;
   kmer_release(h);
-  if (h->win_seg_d) (void)hipFree(h->win_seg_d);
-  if (h->alt_w_d) (void)hipFree(h->alt_w_d);
-  if (h->copy_w_d) (void)hipFree(h->copy_w_d);
-  if (h->fc_perm_d) (void)hipFree(h->fc_perm_d);
-  if (h->seg_var_d) (void)hipFree(h->seg_var_d);
-  if (h->win_off_d) (void)hipFree(h->win_off_d);
-  if (h->win_row_d) (void)hipFree(h->win_row_d);
-  for (float* p : h->fk_seq)
-    if (p) (void)hipFree(p);
-  for (float* p : h->fk_aseq)
-    if (p) (void)hipFree(p);
-  if (h->seam) (void)hipFree(h->seam);
-  if (h->edge) (void)hipFree(h->edge);
   for (void* p : h->allocs) (void)hipFree(p);
   for (hipEvent_t e : h->ev_pool) (void)hipEventDestroy(e);
   for (hipEvent_t e : h->pev)
@@ -3760,7 +3673,7 @@ void expecto_beluga_destroy(expecto_beluga_t h) {
     if (h->stage_ev[s]) (void)hipEventDestroy(h->stage_ev[s]);
   }
   if (h->hflags) (void)hipHostFree(h->hflags);
-  delete h;
+  delete h;   // (its DevBuf members free their memory)
 }
 
 size_t expecto_beluga_device_bytes(expecto_beluga_t h) {
@@ -3813,7 +3726,7 @@ int expecto_beluga_forward_onehot(expecto_beluga_t h, const float* x, int n, flo
       int rc;
       if (as_codes) {
         {
-          LayerTimer lt(h, 0, st);
+          Timer lt(h, 0, st);
           const long long q = (long long)nb * (kLen / 4);
           onehot_codes<<<dim3((unsigned)((q + 255) / 256)), dim3(256), 0, st>>>(x + r0 * 4 * kLen, nb, kLen,
                                                                               h->oh_codes, bad);
@@ -3840,19 +3753,13 @@ int expecto_beluga_forward_onehot(expecto_beluga_t h, const float* x, int n, flo
       EXPECTO_HIP_CHECK(hipMemsetAsync(h->ovf, 0, sizeof(int), st));
       return run_checked(h, st, [&]() { return run(false, nullptr); });
     }
-    if (!flags[0]) return EXPECTO_OK;
-    EXPECTO_HIP_CHECK(hipMemsetAsync(h->ovf, 0, sizeof(int), st));   // as run_checked: bf16x6 redo
-    h->fallbacks += 1;
-    h->precision = EXPECTO_PRECISION_BF16X6;
-    rc = run(true, nullptr);
-    h->precision = EXPECTO_PRECISION_F16X3;
-    return rc;
+    return flags[0] ? rerun_bf16x6(h, st, [&]() { return run(true, nullptr); }) : (int)EXPECTO_OK;
   }
   bool as_codes = false;
   if (candidate) {
     int bad = 0;
     {
-      LayerTimer lt(h, 0, st);
+      Timer lt(h, 0, st);
       EXPECTO_HIP_CHECK(hipMemsetAsync(h->oh_bad, 0, sizeof(int), st));
       const long long q = (long long)n * (kLen / 4);
       onehot_codes<<<dim3((unsigned)((q + 255) / 256)), dim3(256), 0, st>>>(x, n, kLen, nullptr, h->oh_bad);
@@ -3985,14 +3892,9 @@ int expecto_beluga_get_precision(expecto_beluga_t h) { return h ? h->precision :
 
 int expecto_beluga_set_profiling(expecto_beluga_t h, int on) {
   EXPECTO_REQUIRE(h != nullptr, "null handle");
-  if (on && h->ev_pool.empty()) {
-    h->ev_pool.resize(1024);
-    for (auto& e : h->ev_pool) EXPECTO_HIP_CHECK(hipEventCreate(&e));
-  }
-  if (!on) {
-    int rc = resolve_events(h);
-    if (rc) return rc;
-  }
+  int rc;
+  if (on && h->ev.capacity() == 0 && (rc = grow_event_pool(h, 512))) return rc;
+  if (!on && (rc = resolve_events(h))) return rc;
   h->profiling = on != 0;
   if (on) {
     if (h->macs_d) {

@@ -139,6 +139,7 @@ class VariantPipeline:
         self.lib = _lib.load()
         self.use_segments = use_segments
         self.use_pairs = use_pairs
+        self.last_recomputed_slices = 0   # of the last recompute_overflowed call
 
     def prepare(self, vs: VariantSet, shifts, rows: str = "shift") -> dict:
         """Host checks + the device-resident variant tables (done once, outside the hot loop).
@@ -362,6 +363,7 @@ class VariantPipeline:
         number of slices whose rows were recomputed (all `parts` slices in the second case)."""
         eng = self.engine
         n = len(vs)
+        self.last_recomputed_slices = 0
         if n == 0:
             return 0
         bounds = np.unique(np.linspace(0, n, min(parts, n) + 1).round().astype(int))

@@ -7,7 +7,8 @@ table state:
 * forward_codes after load_state_dict runs on tables rebuilt for the new weights (oracle parity);
 * base codes >= 5 read as the zero column (code 4), as conv1 reads them, on every table path;
 * a handle that cannot hold the tables says so (conv2_table_state, one stderr line) and stays at
-  the parity bar; shared tables count once in device_bytes.
+  the parity bar; shared tables count once in device_bytes;
+* the profiling timers' event pool survives being cycled (its rules: tests/test_event_pairs.py).
 """
 import math
 import os
@@ -174,3 +175,34 @@ def test_shared_tables_count_once_in_device_bytes():
     del ea, a
     gc.collect()
     assert eb.device_bytes() == own_b + table
+
+
+def test_profiling_counts_survive_cycling_the_event_pool(monkeypatch):
+    """forward_codes on 4 windows with conv1 and conv2 launched (EXPECTO_CONV2_TABLE=0), profiled for 8
+    calls and then for 80: about 14 event pairs per call, so the 80 calls cycle the 512-pair pool
+    twice.  Every slot's launch count and the full-size conv launches' are exactly 10 times the 8-call
+    figures, and every time is finite and not negative."""
+    m = _model(max_batch=8, env={"EXPECTO_CONV2_TABLE": "0"}, monkeypatch=monkeypatch)
+    eng = m.engine()
+    codes = torch.from_numpy(_codes(4, 5)).cuda()
+    convs = ["conv2", "conv3", "conv4", "conv5", "conv6"]
+    m.forward_codes(codes)                                   # lazily allocated buffers
+    stats = {}
+    for calls in (8, 80):
+        eng.set_profiling(True)
+        try:
+            for _ in range(calls):
+                m.forward_codes(codes)
+            stats[calls] = eng.layer_times(), {c: eng.main_launches(c) for c in convs}
+        finally:
+            eng.set_profiling(False)
+    (lt8, ml8), (lt80, ml80) = stats[8], stats[80]
+    print({k: v[1] for k, v in lt8.items()}, {c: ml8[c][2] for c in convs})
+    assert sum(v[1] for v in lt80.values()) + sum(ml80[c][2] for c in convs) > 2 * 512   # event pairs taken
+    for slot in lt8:
+        assert lt80[slot][1] == 10 * lt8[slot][1], (slot, lt8[slot], lt80[slot])
+        for ms in (lt8[slot][0], lt80[slot][0]):
+            assert math.isfinite(ms) and ms >= 0.0, (slot, ms)
+    for c in convs:
+        assert ml8[c][2] == 8 and ml80[c][2] == 80 and ml80[c][0] == ml8[c][0] > 0, (c, ml8[c], ml80[c])
+        assert math.isfinite(ml80[c][1]) and ml80[c][1] >= 0.0, (c, ml80[c])
