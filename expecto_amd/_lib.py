@@ -103,6 +103,13 @@ SIGNATURES = {
     "expecto_tfidf_transform": (ctypes.c_int, [c_vp, ctypes.c_longlong, ctypes.c_longlong, c_vp, ctypes.c_int, c_vp,
                                                c_vp, ctypes.c_longlong, ctypes.c_int, c_vp, c_vp, ctypes.c_size_t,
                                                c_vp]),
+    "expecto_kmeans_workspace": (ctypes.c_size_t, [ctypes.c_longlong] * 5),
+    "expecto_kmeans_plusplus": (ctypes.c_int, [c_vp, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong,
+                                               ctypes.c_longlong, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t,
+                                               c_vp]),
+    "expecto_kmeans_lloyd": (ctypes.c_int, [c_vp, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong,
+                                            ctypes.c_longlong, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
+                                            ctypes.c_size_t, c_vp]),
     "expecto_last_error": (ctypes.c_char_p, []),
     "expecto_version": (ctypes.c_char_p, []),
 }

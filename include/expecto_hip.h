@@ -46,6 +46,9 @@
  *   expecto_tfidf_stats / _gram    tf-idf of the mark tracks and its float64 Gram matrix (svd.py:76-85)
  *   expecto_tfidf_project          components_ of the truncated SVD (svd.py:84-85)
  *   expecto_tfidf_transform        svd.transform(tf_idf) (svd_transform.py:80)
+ *   expecto_kmeans_plusplus        the k-means++ seeding and
+ *   expecto_kmeans_lloyd           the Lloyd iteration of KMeans(n_clusters=k).fit(X), batched over k and
+ *                                  restarts (cluster_and_viz.py:45-58, the elbow sweep among them)
  *   expecto_beluga_destroy         (model teardown)
  */
 #ifndef EXPECTO_HIP_H
@@ -490,6 +493,68 @@ size_t expecto_tfidf_transform_workspace(int m, int k, long long n);
 int expecto_tfidf_transform(const float* D, long long n, long long ld, const int* keep_idx, int m, const double* idf,
                             const float* V, long long ld_v, int k, double* X_acc, void* workspace,
                             size_t workspace_bytes, void* stream);
+
+/* k-means of the marks' SVD coordinates (cluster_and_viz.py:45-58: KMeans(n_clusters=k).fit(X), and the
+ * commented-out elbow sweep over k), as P independent problems on one matrix per call.  X (DEVICE) is
+ * float64 [n, d] with row stride ld >= d; the padding is never read.  Every problem of a call runs at
+ * the same time, one workgroup each, and neither kernel returns to the host between seeding steps or
+ * iterations.  Supported: 1 <= n <= 4096, 1 <= d <= 128, 1 <= k <= min(n, 512), 1 <= T <= 8,
+ * 0 <= P <= 1048576; everything else is EXPECTO_EINVAL with a message.  P = 0 writes nothing and
+ * succeeds, whatever the pointers are.
+ *
+ * Problem tables.  A call's problems are the rows of an int64 table [P, 8], passed twice with the same
+ * contents: in HOST memory (checked here) and in DEVICE memory (read by the kernel, which passes over
+ * a row that does not fit the checked sizes).  Columns of a seeding row:
+ *   0 k   1 first (the first centre's point index)   2 T (trials per step; sklearn's 2 + int(ln k))
+ *   3 offset of the problem's uniforms in u (float64 elements)   4 offset of its k indices in idx
+ *   5 offset of its k centres in `centres`, in rows of d
+ * and of a Lloyd row:
+ *   0 k   1 max_iter (>= 1)   2 offset of its k initial centres in init, in rows of d
+ *   3 offset of its k centres in `centres`, in rows of d   4 offset of its n labels in labels
+ * Columns not named are ignored.  Every offset column starts at 0 in row 0, and row p + 1's block
+ * starts at or after the end of row p's (refused otherwise: not 0, decreasing, overlapping).  Also
+ * refused: k > n, first outside [0, n), ld < d, a null pointer with P > 0, a workspace smaller than
+ * expecto_kmeans_workspace(n, d, max k, max T, P) bytes (a pure host function that covers either
+ * call; 0 for a refused shape) or not 8-byte aligned.
+ *
+ * The arithmetic is fixed.  All of it is float64, products and sums rounded separately (no FMA), no
+ * atomics: two identical calls give identical bits, and a problem's bits depend neither on the other
+ * rows of the table nor on the launch geometry.
+ *   d2(x, c):  s = +0.0; for j = 0..d-1 in order t = x[j] - c[j], s = s + t*t.
+ *   sequential sum of a[0..m):  s = +0.0, then s = s + a[i] for i ascending (np.cumsum(a)[-1],
+ *     np.add.at): one chain of rounded adds, never a tree.
+ *
+ * expecto_kmeans_plusplus: sklearn's greedy k-means++ with the caller's random numbers.  u (DEVICE):
+ * per problem float64 [k-1, T] uniforms in [0, 1).  closest[i] = d2(X[i], X[first]), pot = sequential
+ * sum of closest.  Step c = 1..k-1: cum = the sequential prefix sums of closest; for t < T
+ * cand[t] = min(first i with cum[i] >= u[c-1,t]*pot, n-1) (np.searchsorted left, clipped);
+ * dc[t][i] = min(closest[i], d2(X[i], X[cand[t]])), pots[t] = sequential sum of dc[t]; the winner is
+ * the first t of minimal pots[t]; pot = pots[t], closest = dc[t], idx[c] = cand[t].  idx[0] = first.
+ * Outputs (DEVICE): idx int32, the k chosen point indices; centres float64 [k, d], copies of those rows.
+ *
+ * expecto_kmeans_lloyd: sklearn's _kmeans_single_lloyd.  tol (DEVICE) float64 [P], absolute; init
+ * (DEVICE) float64, per problem [k, d].  One iteration:
+ *   E-step      label[i] = the lowest c of minimal d2(X[i], C[c]); dist[i] that minimum.
+ *   relocation  the e clusters without a label, ascending, receive the e points of largest dist in
+ *               descending order, equal dist to the lower point index; such a point counts for its new
+ *               cluster and not for its old one in this M-step only; label is unchanged by it.
+ *   M-step      sum[c][j] = +0.0, then + X[i][j] over the cluster's members in ascending i;
+ *               C_new[c] = sum[c] / (double)count[c] (IEEE division); a cluster still empty keeps its centre.
+ *   shift       the sequential sum over (c, j) row-major of (C_new - C)^2;  then C = C_new.
+ *   stop        strictly if label equals the previous iteration's (none before the first); else if
+ *               shift <= tol; else continue, up to max_iter iterations.
+ * After a stop that was not strict one more E-step runs against the final centres.  Outputs (DEVICE):
+ * labels int32 [n] per problem, centres float64 [k, d] per problem, inertia float64 [P] = the
+ * sequential sum over i of d2(X[i], C[label[i]]) against the final centres, n_iter int32 [P] = the
+ * iterations run. */
+size_t expecto_kmeans_workspace(long long n, long long d, long long k_max, long long t_max, long long P);
+int expecto_kmeans_plusplus(const double* X, long long n, long long d, long long ld, long long P,
+                            const long long* prob_host, const long long* prob, const double* u, int* idx,
+                            double* centres, void* workspace, size_t workspace_bytes, void* stream);
+int expecto_kmeans_lloyd(const double* X, long long n, long long d, long long ld, long long P,
+                         const long long* prob_host, const long long* prob, const double* tol, const double* init,
+                         int* labels, double* centres, double* inertia, int* n_iter, void* workspace,
+                         size_t workspace_bytes, void* stream);
 
 const char* expecto_last_error(void);
 const char* expecto_version(void);
