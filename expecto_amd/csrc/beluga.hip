@@ -625,6 +625,9 @@ constexpr int kW4u = 19, kA4u = 26;   // conv4 run [r3 - 7, r3 + 12): the 12 cha
 struct SegDims {
   int L, T1, P1, T3, T4, S5, T5, T6;
 };
+static_assert(kSegW[1] == kDW[1] && kSegW[2] == kDW[2] && kSegW[3] == kDW[3] && kSegW[4] == kW4u && kSegW[5] == kDW[4] &&
+                  kSegW[6] == kDW[5] && kSegW6 == kDW[6],
+              "seg_plan.h seg_r6 restates seg_delta_table's run widths");
 
 // (block m of the chunk = entry e0 + m, SegStrands)
 __global__ void seg_delta_table(const int* __restrict__ var_pos, int e0, int ns, SegStrands ss, SegDims g, int n_ph,
@@ -886,15 +889,12 @@ __global__ void pair_rows(long long* __restrict__ c_rows, int M, int nv, int v0,
 // of the 9 products are formed once per handle in fp64 and rounded to fp32 once; the sequences
 // are formed in fp32 from the stored f16x3 planes and stored as planes (22-bit) like any
 // activation.  tests/test_fc1_karatsuba_identity.py checks the algebra in float64.
-constexpr int kFkK = 16000;                        // one 25-row block of conv6 rows (25 x 640)
+// (kFkK = 16000, one 25-row block of conv6 rows; kFkSlabs = 2 K slabs per product, 250 K blocks as
+// FC1's 265; kFkSeq, kFkBlk, kFkRole: seg_plan.h, where the host planner reads them too)
 constexpr int kFkKb = kFkK / GBK;                  // 500 K blocks
-constexpr int kFkSlabs = 2;                        // K slabs per product (250 K blocks, as FC1's 265)
 constexpr int kFkTailK = kFc1In - 4 * kFkK;        // 3840: rows 100..105
 constexpr int kFkKbTotal = 9 * kFkKb + kFkTailK / GBK;   // 4620 K blocks per weight row
 constexpr long long kFkKTotal = 9LL * kFkK + kFkTailK;   // 147,840
-constexpr int kFkSeq[9] = {3, 2, 3, 1, 0, 1, 3, 2, 3};   // product g reads sequence (0 x, 1 D1, 2 D2, 3 DD)
-constexpr int kFkBlk[9] = {0, 1, 1, 2, 3, 3, 2, 3, 3};   //   at block kFkBlk[g] of its group
-constexpr int kFkRole[4][4] = {{0, 1, 3, 4}, {1, 2, 4, 5}, {3, 4, 6, 7}, {4, 5, 7, 8}};
 constexpr int kFkW[9][4] = {{1, 0, 0, 0}, {1, 1, 0, 0}, {0, -1, 0, 0}, {1, 0, 1, 0}, {1, 1, 1, 1},
                             {0, -1, 0, -1}, {0, 0, -1, 0}, {0, 0, -1, -1}, {0, 0, 0, 1}};   // V_q coefficients
 constexpr int kFkParts = 4 * kFkSlabs + 1;         // partial rows a window's FC1 sums (8 + the tail)
@@ -2460,7 +2460,10 @@ bool fk_use_seg(const expecto_beluga* h) { return h->fk_on && h->fkw && g_precis
 
 // Table buffers, allocated with the first Karatsuba FC1: group starts (9 lists of <= max_batch),
 // window starts, kFkParts partial rows per window, kFkParts x tiles alt-mask words.
-int fk_cap(const expecto_beluga* h) { return std::max(h->max_batch, h->fk_slice); }
+int fk_cap(const expecto_beluga* h) {
+  const long long dflt = std::min<long long>((long long)kFkSlicePerBatch * h->max_batch, 1LL << 30);
+  return std::max(h->max_batch, h->fk_slice ? h->fk_slice : (int)dflt);
+}
 // fk_gres entries per max_batch: a segment chunk's conv6 blocks nb keep their conv5 rows in Q,
 // nb * T5 * 640 <= max_batch * 496 * 320 with T5 >= 113 (segments of >= 2000 bases): nb < 2.2 max_batch
 constexpr int kGresPerBatch = 3;
@@ -2480,9 +2483,10 @@ int fk_tables(expecto_beluga* h) {
   return EXPECTO_OK;
 }
 
-// Segment-path FC1 launches of up to fk_cap windows (the 200-window workload's 2 x 19,200 windows
-// in launches of 24,576 + 13,824: one round structure each instead of part-filled ones): partial rows,
-// FC1 output rows, window starts and output rows, allocated with the first segment call.
+// Segment-path FC1 launches of up to fk_cap rows -- windows, and the alt windows of segment pairs
+// once more (SegPlan::fk_slice; the 200-window workload's chunk of 38,400 windows + 1,920 alt
+// windows is one launch): partial rows, FC1 output rows, window starts and output rows, allocated
+// with the first segment call.
 int fk_seg_buffers(expecto_beluga* h) {
   if (h->fk_part) return EXPECTO_OK;
   const size_t cap = fk_cap(h);
@@ -2535,6 +2539,20 @@ struct FkProducts {
   int lay[9];   // partial-row layout counts (0: cnt); an in-place alt launch runs cnt <= lay rows of the ref layout
 };
 
+// Alt rows of a grouped launch (segment pairs, out of place; SegPlan::fk_alt_plan): per product g and
+// K slab s, cnt[g][s] alt group starts at g_rows + off[g][s]; then the tails of n_tail alt windows
+// (w_rows: their starts).  A: the alt blocks x and their sequences seq.  Their partial rows follow
+// each other from row0 of the launch's `part`, in that order.
+struct FkAltRows {
+  const float* x;
+  const DevBuf<float>* seq;
+  const long long* g_rows;
+  int off[9][kFkSlabs], cnt[9][kFkSlabs];
+  const long long* w_rows;
+  int n_tail;
+  long long row0;
+};
+
 // FC1 output rows of n windows from their kFkParts partial rows each (prow), fk_reduce_h2
 int fk_reduce(expecto_beluga* h, const float* part, const int* prow, int n, float* h1, hipStream_t st) {
   Timer lt(h, 7, st);
@@ -2574,10 +2592,12 @@ bool fc_skinny(const expecto_beluga* h, long long rows) {
 // kFkSlabs K slabs, then the tail over the windows (w_rows: window starts), as split-K partial rows
 // of `part` in that order (the layout prow was built for); then fk_reduce_h2 into h1.  x: conv6 rows
 // (the product X@3 and the tail), seq: their D1 / D2 / DD.  mask (alt, in place): descriptor d runs
-// only the M tiles with bit 0 of mask[d * tiles + tile] set.
+// only the M tiles with bit 0 of mask[d * tiles + tile] set.  alt (no mask): its descriptors ride in
+// the same launch, the product ones after the ref products and its tail last, so the short tail
+// tiles (120 K blocks against 250) stay at the end of the launch.
 int fk_fc1(expecto_beluga* h, const float* x, const DevBuf<float>* seq, const FkProducts& pr, const long long* w_rows, int n,
            const int* prow, float* h1, hipStream_t st, const unsigned* mask = nullptr, int tiles = 0,
-           float* part = nullptr, long long part_cap = 0) {
+           float* part = nullptr, long long part_cap = 0, const FkAltRows* alt = nullptr) {
   if (!part) {
     part = h->part;
     part_cap = (long long)std::max(h->fc_splits, kFkParts) * h->max_batch;
@@ -2592,13 +2612,17 @@ int fk_fc1(expecto_beluga* h, const float* x, const DevBuf<float>* seq, const Fk
   long long blk = 0;
   int mslot = 0;   // mask slot: descriptor order of the full layout (2 per product in use, then the tail)
   double macs = 0.0;
-  auto add = [&](const float* A, const long long* ar, long long aoff, int kb0, int nk, int M, int lay) {
+  auto add = [&](const float* A, const long long* ar, long long aoff, int kb0, int nk, int M, long long crow) {
+    if (G.n >= FCK_MAX) {
+      ++G.n;   // (refused below)
+      return;
+    }
     FcDesc& d = G.d[G.n];
     d.A = A;
     d.a_rows = ar;
     d.a_off = aoff;
     d.Bp = wb + (long long)kb0 * 128;
-    d.C = part + row * kHidLd;
+    d.C = part + crow * kHidLd;
     d.mask = mask ? mask + (size_t)mslot * tiles : nullptr;
     ++mslot;
     d.M = M;
@@ -2606,7 +2630,6 @@ int fk_fc1(expecto_beluga* h, const float* x, const DevBuf<float>* seq, const Fk
     d.nk = nk;
     d.blk0 = (int)blk;
     blk += (long long)d.m_tiles * G.n_tiles;
-    row += lay;
     macs += (double)M * kFc1Out * nk * GBK;
     ++G.n;
   };
@@ -2615,16 +2638,31 @@ int fk_fc1(expecto_beluga* h, const float* x, const DevBuf<float>* seq, const Fk
     for (int s = 0; lay > 0 && s < kFkSlabs; ++s) {
       if (pr.cnt[g] > 0)
         add(kFkSeq[g] ? seq[kFkSeq[g] - 1].p : x, pr.g_rows + pr.off[g], 25LL * kFkBlk[g] * 640 + (long long)s * kFkK / kFkSlabs,
-            g * kFkKb + s * kFkKb / kFkSlabs, kFkKb / kFkSlabs, pr.cnt[g], lay);
-      else {
-        row += lay;   // (in-place alt launch: no alt group needs this product; keep the ref layout)
-        ++mslot;
-      }
+            g * kFkKb + s * kFkKb / kFkSlabs, kFkKb / kFkSlabs, pr.cnt[g], row);
+      else
+        ++mslot;   // (in-place alt launch: no alt group needs this product; keep the ref layout)
+      row += lay;
     }
   }
-  add(x, w_rows, 100LL * 640, 9 * kFkKb, kFkTailK / GBK, n, n);
+  const long long tail_row = row;
+  row += n;
+  long long arow = alt ? alt->row0 : row;
+  EXPECTO_REQUIRE(!(alt && mask) && arow >= row, "Karatsuba FC1 alt rows");
+  for (int g = 0; alt && g < 9; ++g)
+    for (int s = 0; s < kFkSlabs; ++s) {
+      if (alt->cnt[g][s] <= 0) continue;
+      add(kFkSeq[g] ? alt->seq[kFkSeq[g] - 1].p : alt->x, alt->g_rows + alt->off[g][s],
+          25LL * kFkBlk[g] * 640 + (long long)s * kFkK / kFkSlabs, g * kFkKb + s * kFkKb / kFkSlabs, kFkKb / kFkSlabs,
+          alt->cnt[g][s], arow);
+      arow += alt->cnt[g][s];
+    }
+  add(x, w_rows, 100LL * 640, 9 * kFkKb, kFkTailK / GBK, n, tail_row);
+  if (alt && alt->n_tail > 0) {
+    add(alt->x, alt->w_rows, 100LL * 640, 9 * kFkKb, kFkTailK / GBK, alt->n_tail, arow);
+    arow += alt->n_tail;
+  }
   EXPECTO_REQUIRE(G.n <= FCK_MAX && blk < (1LL << 31), "Karatsuba FC1 descriptors");
-  EXPECTO_REQUIRE(row <= part_cap, "Karatsuba FC1 partial rows");
+  EXPECTO_REQUIRE(arow <= part_cap, "Karatsuba FC1 partial rows");
   {
     Timer lt(h, 6, st);
     if (h->profiling) {
@@ -2905,11 +2943,13 @@ int seg_fc2(const SegCall& c, const float* h1, int n, float* y, const long long*
 
 // The alt conv6 blocks of the chunk into Q (conv5 rows are dead): only the rows the alt windows
 // read, once the alt conv6 runs (and the Q reads of their patches) are done
-int seg_alt_conv6(const SegCall& c, const SegChunk& ck) {
+// (on st; or on sa, in order behind the alt runs, once st's ref conv6 -- P written, Q's conv5 rows read -- is done)
+int seg_alt_conv6(const SegCall& c, const SegChunk& ck, bool on_sa = false) {
   int rc;
-  if ((rc = seg_st_wait(c, c.h->pev[13]))) return rc;
-  seg_alt_blocks<<<dim3(kAltRows6, (unsigned)ck.nb), dim3(64), 0, c.st>>>(c.h->P, c.h->D0, c.pl.n_ph, c.pl.g.T6,
-                                                                           c.h->seg_tab, 640 * c.eb / 16, c.h->Q);
+  const hipStream_t s = on_sa ? c.sa : c.st;
+  if ((rc = s == c.st ? seg_st_wait(c, c.h->pev[13]) : stream_order(c.st, s, c.h->pev[14]))) return rc;
+  seg_alt_blocks<<<dim3(kAltRows6, (unsigned)ck.nb), dim3(64), 0, s>>>(c.h->P, c.h->D0, c.pl.n_ph, c.pl.g.T6,
+                                                                        c.h->seg_tab, 640 * c.eb / 16, c.h->Q);
   return check_launch("seg_alt_blocks");
 }
 
@@ -3084,13 +3124,96 @@ FkAltTables fk_alt_tables(const SegPlan& pl, const std::vector<FkWin>& ws, const
   return t;
 }
 
+// The alt conv6 blocks of the chunk (Q) and their D1 / D2 / DD, once per chunk: on st, or on the alt
+// stream beside st's ref sequences (st then waits for pev[15] before it reads them)
+int seg_alt_sequences(const SegCall& c, const SegChunk& ck, bool on_sa) {
+  expecto_beluga* h = c.h;
+  on_sa = on_sa && c.sa != c.st;
+  int rc;
+  if ((rc = seg_alt_conv6(c, ck, on_sa))) return rc;
+  DeltaScope ds(h);
+  if ((rc = fk_sequences(h, h->Q, ck.nb, c.pl.g.T6, c.pl.g.T6, h->seg_tab, c.pl.n_ph, on_sa ? c.sa : c.st, h->fk_gres, 1)))
+    return rc;
+  if (on_sa) EXPECTO_HIP_CHECK(hipEventRecord(h->pev[15], c.sa));
+  return EXPECTO_OK;
+}
+
+// Tables of a Karatsuba slice whose alt work rides in the ref launch (host only; ap: the planner's
+// alt rows, SegPlan::fk_alt_plan): the alt group-start lists and the reached alt windows' starts
+// appended to grows, the alt windows' partial rows appended to prow -- per part the alt row where
+// the SNV reaches it, else the ref row of the same group or window -- and the windows of the
+// slice's FC1 output rows, the ref windows and then the alt windows.
+struct FkAltRowTables {
+  FkAltRows ar;           // g_rows / w_rows as offsets into grows (the caller adds the device base)
+  size_t w_off;
+  std::vector<int> perm;
+  long long rows;         // alt partial rows
+};
+FkAltRowTables fk_alt_row_tables(const std::vector<FkWin>& ws, const FkSlice& sl, const FkAltPlan& ap, int T6,
+                                 long long row0, std::vector<long long>& grows, std::vector<int>& prow) {
+  FkAltRowTables t{};
+  t.ar.row0 = row0;
+  std::vector<long long> gst;   // the alt groups' starts, as fk_slice_tables forms them
+  for (size_t i = sl.i0; i < sl.i0 + sl.nw_pre; ++i)
+    if (i == sl.i0 || !fk_same_group(ws[i], ws[i - 1]))
+      gst.push_back(((long long)ws[i].blk * T6 + fk_group_of(ws[i].off6)) * 640);
+  long long base[9][kFkSlabs] = {}, row = row0;
+  for (int g = 0; g < 9; ++g)
+    for (int sb = 0; sb < kFkSlabs; ++sb) {
+      const std::vector<int>& l = ap.grp[g][sb];
+      t.ar.off[g][sb] = (int)grows.size();
+      t.ar.cnt[g][sb] = (int)l.size();
+      base[g][sb] = row;
+      row += (long long)l.size();
+      for (int k : l) grows.push_back(gst[(size_t)k]);
+    }
+  t.w_off = grows.size();
+  t.ar.n_tail = (int)ap.tail.size();
+  for (int i : ap.tail) grows.push_back(((long long)ws[sl.i0 + i].blk * T6 + ws[sl.i0 + i].off6) * 640);
+  const long long tail_base = row;
+  t.rows = row + (long long)ap.tail.size() - row0;
+  const int fn = (int)(sl.i1 - sl.i0);
+  for (int i = 0; i < fn; ++i) t.perm.push_back(ws[sl.i0 + i].w);
+  auto pos_in = [](const std::vector<int>& l, int v) {   // index of v in the ascending list l, or -1
+    const auto it = std::lower_bound(l.begin(), l.end(), v);
+    return it != l.end() && *it == v ? (int)(it - l.begin()) : -1;
+  };
+  int k = -1;
+  size_t next = 0;
+  for (size_t i = 0; i < sl.nw_pre && next < ap.win.size(); ++i) {
+    if (i == 0 || !fk_same_group(ws[sl.i0 + i], ws[sl.i0 + i - 1])) ++k;
+    if ((int)i != ap.win[next]) continue;
+    ++next;
+    const FkWin& w = ws[sl.i0 + i];
+    t.perm.push_back(w.w);
+    const size_t p0 = prow.size();
+    prow.resize(p0 + kFkParts);
+    for (int j = 0; j < kFkParts; ++j) prow[p0 + j] = prow[i * kFkParts + j];
+    for (int j = 0; j < 4; ++j) {
+      const int g = kFkRole[fk_role_of(w.off6)][j];
+      for (int sb = 0; sb < kFkSlabs; ++sb) {
+        const int at = pos_in(ap.grp[g][sb], k);
+        if (at >= 0) prow[p0 + kFkSlabs * j + sb] = (int)(base[g][sb] + at);
+      }
+    }
+    const int at = pos_in(ap.tail, (int)i);
+    if (at >= 0) prow[p0 + kFkParts - 1] = (int)(tail_base + at);
+  }
+  return t;
+}
+
 // FC stage of a chunk, FC1 as the block Karatsuba: the conv6 blocks' D1 / D2 / DD, then slices of
-// whole window groups (<= fk_cap windows, SegPlan::fk_slice) in group order: window starts and output
+// whole window groups (<= fk_cap rows, SegPlan::fk_slice) in group order: window starts and output
 // rows (seg_a_rows), the slice's product and partial-row tables (host, staged), one grouped FC1
-// launch, FC2.  Segment pairs: the groups holding alt windows come first in the first slice; right
-// after it, the alt FC1 runs IN PLACE over that slice's partial rows -- the alt blocks' sequences
-// (Q), only the (product, slab, tail) partials the SNV's changed conv6 rows reach (masks per
-// M tile), the ref partials for the rest -- and the alt windows' rows are reduced and FC2'd.
+// launch, one reduction, FC2.  Segment pairs: the groups holding alt windows come first, and their
+// alt work is more rows of the same launch -- per (product, slab) the alt groups whose partial the
+// SNV's changed conv6 rows reach, and the reached tails, read from the alt blocks (Q) and their
+// sequences and written after the ref partial rows; an alt window's other parts are its ref partial
+// rows (fk_alt_row_tables), so the reduction forms the ref and the alt FC1 rows together.  The alt
+// blocks and their sequences are formed on the alt stream beside the ref sequences.
+// EXPECTO_FC1K_ALT_INPLACE=1 (and a slice whose tables do not fit its buffers): the alt FC1 runs
+// after the slice's ref FC stage, IN PLACE over its partial rows, masked per M tile, with a reduction
+// and an FC2 of its own.  The same partials summed in the same order either way: the same bits.
 int seg_fc_karatsuba(const SegCall& c, const SegChunk& ck) {
   expecto_beluga* h = c.h;
   const SegPlan& pl = c.pl;
@@ -3103,9 +3226,16 @@ int seg_fc_karatsuba(const SegCall& c, const SegChunk& ck) {
   const std::vector<int> gres = pl.fk_gres(ck.ci);
   EXPECTO_REQUIRE(nb <= kGresPerBatch * (long long)h->max_batch, "conv6 blocks of a chunk exceed fk_gres");
   if ((rc = stage_copies(h, {{h->fk_gres, gres.data(), gres.size() * sizeof(int)}}, st)) || (rc = fk_tables(h)) ||
-      (rc = fk_seg_buffers(h)) || (rc = fk_sequences(h, h->P, nb, T6, T6, nullptr, n_ph, st, h->fk_gres)))
+      (rc = fk_seg_buffers(h)))
     return rc;
   bool alt_ready = false;   // alt conv6 blocks (Q) and their sequences formed (once per chunk)
+  const bool alt_early = c.pr && !h->fk_alt_inplace && !pl.fk_alt[ck.ci].empty();
+  if (alt_early) {
+    if ((rc = seg_alt_sequences(c, ck, true))) return rc;
+    alt_ready = true;
+  }
+  if ((rc = fk_sequences(h, h->P, nb, T6, T6, nullptr, n_ph, st, h->fk_gres))) return rc;
+  if (alt_early && (rc = seg_st_wait(c, h->pev[15]))) return rc;
   FkSlice sl{};
   for (size_t i0 = 0; i0 < ws.size(); i0 = sl.i1) {
     const char* refusal = pl.fk_slice(ck.ci, i0, sl);
@@ -3115,6 +3245,34 @@ int seg_fc_karatsuba(const SegCall& c, const SegChunk& ck) {
     std::vector<int> prow, rgrp, ginfo;
     FkProducts prd{h->fk_grows, {}, {}, {}};
     fk_slice_tables(ws, (int)i0, (int)sl.i1, T6, grows, prd, prow, &rgrp, &ginfo);
+    if (sl.n_ag > 0 && !h->fk_alt_inplace) {
+      const FkAltPlan ap = pl.fk_alt_plan(ck.ci, sl);
+      const int na = (int)ap.win.size();
+      long long ref_rows = fn, alt_lists = (long long)ap.tail.size();
+      for (int g = 0; g < 9; ++g) {
+        ref_rows += (long long)kFkSlabs * prd.cnt[g];
+        for (int sb = 0; sb < kFkSlabs; ++sb) alt_lists += (long long)ap.grp[g][sb].size();
+      }
+      // (fk_slice counts an alt window twice, so these hold but for a first group above the cap)
+      if (fn + na <= cap && ref_rows + alt_lists <= kFkParts * cap && (long long)grows.size() + alt_lists <= 9 * cap) {
+        FkAltRowTables t = fk_alt_row_tables(ws, sl, ap, T6, ref_rows, grows, prow);
+        t.ar.x = h->Q;
+        t.ar.seq = h->fk_aseq;
+        t.ar.g_rows = h->fk_grows;
+        t.ar.w_rows = h->fk_grows + t.w_off;
+        if ((rc = stage_copies(h, {{h->fk_grows, grows.data(), grows.size() * sizeof(long long)},
+                                   {h->fk_prow, prow.data(), prow.size() * sizeof(int)},
+                                   {h->fk_aperm, t.perm.data(), t.perm.size() * sizeof(int)}}, st)) ||
+            (rc = seg_rows(c, ck, h->fk_aperm, 0, fn + na, h->fk_arows, h->fk_crows)) ||
+            (rc = fk_fc1(h, h->P, h->fk_seq, prd, h->fk_arows, fn, nullptr, h->fk_h1, st, nullptr, 0, h->fk_part,
+                         kFkParts * cap, &t.ar)) ||
+            (rc = fk_reduce(h, h->fk_part, h->fk_prow, fn + na, h->fk_h1, st)) ||
+            (rc = seg_fc2(c, h->fk_h1, fn, c.y, h->fk_crows)) ||
+            (na > 0 && (rc = seg_fc2(c, h->fk_h1 + (long long)fn * kHidLd, na, c.pr->y_alt, h->fk_crows + fn))))
+          return rc;
+        continue;
+      }
+    }
     if ((rc = stage_copies(h, {{h->fk_grows, grows.data(), grows.size() * sizeof(long long)},
                                {h->fk_prow, prow.data(), prow.size() * sizeof(int)}}, st)) ||
         (rc = seg_rows(c, ck, perm + i0, 0, fn, h->fk_arows, h->fk_crows)) ||
@@ -3133,9 +3291,7 @@ int seg_fc_karatsuba(const SegCall& c, const SegChunk& ck) {
                                {h->fk_aprow, t.aprow.data(), t.aprow.size() * sizeof(int)}}, st)))
       return rc;
     if (!alt_ready) {
-      if ((rc = seg_alt_conv6(c, ck))) return rc;
-      DeltaScope ds(h);
-      if ((rc = fk_sequences(h, h->Q, nb, T6, T6, h->seg_tab, n_ph, st, h->fk_gres, 1))) return rc;
+      if ((rc = seg_alt_sequences(c, ck, false))) return rc;
       alt_ready = true;
     }
     EXPECTO_HIP_CHECK(hipMemsetAsync(h->fk_smask, 0, (size_t)(t.md.n + 1) * tiles * sizeof(unsigned), st));
@@ -3237,7 +3393,8 @@ int forward_segments(expecto_beluga* h, const uint8_t* codes, int n_seg, int L, 
   const char* refusal = nullptr;
   if (seg_plan({n_seg, L, mode, win_seg, win_off, win_row, n_win, pr ? pr->var_pos : nullptr,
                 pr ? pr->strand_stride : n_win, h->max_batch, p_floats(h->max_batch) - 16 * 640,
-                q_floats(h->max_batch) - 16 * 640, h->seg_merge_strands, h->seg_chunk_windows, fk_use_seg(h), fk_cap(h)},
+                q_floats(h->max_batch) - 16 * 640, h->seg_merge_strands, h->seg_chunk_windows, fk_use_seg(h), fk_cap(h),
+                h->fk_alt_inplace},
                pl, &refusal)) {
     set_error(refusal);
     return EXPECTO_EINVAL;

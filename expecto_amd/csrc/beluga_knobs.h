@@ -20,6 +20,11 @@ constexpr int kFcSplitsDefault = 8;    // round 2 sweep (tools/knob_sweep.py, in
                                        // +0.6-0.9 % on the 200-window workload, +0.3-1.2 % on configs[1]
                                        // (4: -0.6 / -3.7 %), with 2.5x less split-K partial traffic
 
+// Default Karatsuba FC1 slice of the segment path, in max_batch windows: the 200-window workload's
+// chunk (both strands of 96 SNVs, 38,400 windows at max_batch 8192: 4.69 max_batch) is one slice; a
+// larger chunk runs in slices.  The slice's buffers (beluga.hip fk_seg_buffers) are sized by it.
+constexpr int kFkSlicePerBatch = 5;
+
 struct BelugaKnobs {
   bool overlap = true;                //   EXPECTO_OVERLAP=0: one stream (same bits either way)
   int fc_splits = kFcSplitsDefault;   // FC1 split-K slabs: a divisor of 2120 K blocks, <= 32
@@ -45,7 +50,10 @@ struct BelugaKnobs {
   double kmer_max_bytes = std::numeric_limits<double>::infinity();   //   cap on the table's bytes (EXPECTO_KMER_MAX_BYTES)
   bool fk_on = true;                  // f16x3 FC1 as a block-Karatsuba convolution (EXPECTO_FC1_KARATSUBA)
   int fk_role = 4;                    //   role of per-window forwards (EXPECTO_FC1_ROLE; 4 = direct FC1, the default; 0..3 Karatsuba)
-  int fk_slice = 24576;               //   windows per Karatsuba FC1 launch on the segment path (EXPECTO_FC1K_SLICE)
+  int fk_slice = 0;                   //   cap on the windows per Karatsuba FC1 launch on the segment path (EXPECTO_FC1K_SLICE;
+                                      //   0: kFkSlicePerBatch x max_batch, one launch per chunk of the 200-window workload)
+  bool fk_alt_inplace = false;        //   segment pairs: the alt FC1 as a masked pass of its own over the ref partial rows
+                                      //   (EXPECTO_FC1K_ALT_INPLACE=1); default: alt rows of the ref launch, out of place
   bool onehot_as_codes = true;        // forward_onehot: exact one-hot input through the k-mer gather (EXPECTO_ONEHOT_CODES)
 };
 
@@ -113,6 +121,12 @@ inline constexpr BelugaKnob kBelugaKnobs[] = {
                      "EXPECTO_CONV_TILE must be 0 (auto), 256 or 384"),                  // same bits
 };
 
+// A/B switches: read like the knobs, but no tuning knobs -- each keeps an earlier schedule of the
+// library for comparisons inside one process (INTEGRATION.md lists them below the knob table).
+inline constexpr BelugaKnob kBelugaSwitches[] = {
+    knob_detail::flag("EXPECTO_FC1K_ALT_INPLACE", &BelugaKnobs::fk_alt_inplace),         // same bits
+};
+
 // Fills k from `get` (getenv's signature: the value of a variable, or null).  Returns null, or the
 // refusal of the first knob in the table whose value is not accepted; k is then partly filled.
 template <class Getenv>
@@ -130,6 +144,8 @@ const char* beluga_knobs_parse(BelugaKnobs& k, Getenv&& get) {
       k.*s.i = v;
     }
   }
+  for (const BelugaKnob& s : kBelugaSwitches)
+    if (const char* e = get(s.name)) k.*s.b = atoi(e) != 0;
   return nullptr;
 }
 

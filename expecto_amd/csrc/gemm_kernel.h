@@ -1449,13 +1449,14 @@ __global__ __launch_bounds__(64 * 2 * NB, 2) void beluga_fc_h3s(GemmArgs p) {
 
 // ---- grouped wide FC GEMM: several split-K partial GEMMs in one launch ----------------------
 // FC1's block Karatsuba (beluga.hip, "FC1 as a block-Karatsuba convolution") runs up to 9
-// products x 2 K slabs + the tail per window group as separate GEMMs with their own A rows,
+// products x 2 K slabs + the tail per window group (and, segment pairs, as many again over the alt
+// groups' changed partials) as separate GEMMs with their own A rows,
 // weight planes and partial rows; one launch over all of them fills the chip's rounds as one
 // GEMM would (the r04 probe ran them as 4 launches and lost most of the saving to part-filled
 // rounds).  Descriptor d covers launch blocks [blk0, blk0 + m_tiles * n_tiles), N tiles fastest
 // (the 6 N tiles of an M tile run together; an XCD's ~32 concurrent workgroups share ~5 M tiles'
 // weight tiles, as beluga_fc_h3w's N-fastest order).
-constexpr int FCK_MAX = 24;
+constexpr int FCK_MAX = 40;   // 2 x (9 products x 2 K slabs + the tail): ref and alt rows of one launch, + 2 spare
 struct FcDesc {
   const float* A;            // activation rows (f16x3 planes)
   const long long* a_rows;   // element offset of each of the M rows

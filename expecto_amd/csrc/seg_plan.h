@@ -74,6 +74,48 @@ inline bool fk_same_group(const FkWin& a, const FkWin& b) {
   return a.blk == b.blk && fk_group_of(a.off6) == fk_group_of(b.off6);
 }
 
+// The block-Karatsuba FC1's products (beluga.hip, "FC1 as a block-Karatsuba convolution"): product g
+// reads one sequence at one 25-row block of its group, in kFkSlabs K slabs; a window in role a sums
+// the products kFkRole[a].
+constexpr int kFkK = 16000;                              // one 25-row block of conv6 rows (25 x 640)
+constexpr int kFkSlabs = 2;                              // K slabs per product
+constexpr int kFkSeq[9] = {3, 2, 3, 1, 0, 1, 3, 2, 3};   // product g reads sequence (0 x, 1 D1, 2 D2, 3 DD)
+constexpr int kFkBlk[9] = {0, 1, 1, 2, 3, 3, 2, 3, 3};   //   at block kFkBlk[g] of its group
+constexpr int kFkRole[4][4] = {{0, 1, 3, 4}, {1, 2, 4, 5}, {3, 4, 6, 7}, {4, 5, 7, 8}};
+
+// Segment pairs: the first changed conv6 row of a (segment, pool2 phase p) block whose SNV is at
+// base q of the segment in the block's strand orientation -- seg_delta_table's arithmetic (beluga.hip)
+// on the host.  The alt block differs from the ref block in rows [r6, r6 + kSegW6) only.
+constexpr int kSegW[7] = {0, 8, 5, 12, 19, 6, 13};       // run widths: conv1, conv2+pool1, conv3, conv4, pool2, conv5
+constexpr int kSegW6 = 20;                               //   and conv6
+inline int seg_floor4(int v) { return v >= 0 ? v >> 2 : -((3 - v) >> 2); }
+inline int seg_clamp(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+inline int seg_r6(const SegGeo& g, int q, int p) {
+  const int r1 = seg_clamp(q - 7, 0, g.T1 - kSegW[1]);
+  const int r2 = seg_clamp(seg_floor4(r1 - 7), 0, g.P1 - kSegW[2]);
+  const int r3 = seg_clamp(r2 - 7, 0, g.T3 - kSegW[3]);
+  const int r4 = seg_clamp(r3 - 7, 0, g.T4 - kSegW[4]);
+  const int r4p = seg_clamp(seg_floor4(r4 - p), 0, g.S5 - kSegW[5]);
+  const int r5 = seg_clamp(r4p - 7, 0, g.T5 - kSegW[6]);
+  return seg_clamp(r5 - 7, 0, g.T6 - kSegW6);
+}
+
+// Does the partial (product g, K slab s) of the group that starts at conv6 row G read a changed row
+// of its block, [r6, r6 + kSegW6)?  The slab's rows of the product's block, with the lags of its
+// sequence (D1: 25; D2: 50; DD: 25, 50, 75).  The tail of a window at off6 reads rows 100..105.
+inline bool fk_reach(int G, int g, int s, int r6) {
+  const int base = G + 25 * kFkBlk[g], per = kFkK / kFkSlabs;
+  const int i0 = base + (s * per) / 640, i1 = base + ((s + 1) * per - 1) / 640;
+  const int sq = kFkSeq[g], nl = sq == 0 ? 1 : sq == 3 ? 4 : 2, lag1 = sq == 2 ? 50 : 25;
+  bool hit = false;
+  for (int l = 0; l < nl; ++l) {
+    const int lag = l == 0 ? 0 : (nl == 2 ? lag1 : 25 * l);
+    hit |= i0 + lag < r6 + kSegW6 && i1 + lag >= r6;
+  }
+  return hit;
+}
+inline bool fk_reach_tail(int off6, int r6) { return off6 + 100 < r6 + kSegW6 && off6 + 105 >= r6; }
+
 // What a segment call is planned from: the caller's host tables and the handle's sizes and knobs.
 struct SegPlanIn {
   int n_seg, L, mode;                          // mode: kStrandFwd / Rc / Both
@@ -87,6 +129,7 @@ struct SegPlanIn {
   int chunk_windows;                           // EXPECTO_SEG_CHUNK_WINDOWS (<= 0: no cap)
   bool fk;                                     // the Karatsuba FC1 is on for segments
   long long fk_cap;                            // windows per Karatsuba FC1 slice
+  bool alt_inplace = false;                    // EXPECTO_FC1K_ALT_INPLACE: the alt FC1 as a pass of its own
 };
 
 // A slice [i0, i1) of a chunk's group order and its leading groups that hold an alt window: n_ag
@@ -94,6 +137,15 @@ struct SegPlanIn {
 struct FkSlice {
   size_t i0, i1, nw_pre;
   int n_ag;
+};
+
+// The alt work of a slice as rows of its grouped FC1 launch (segment pairs, out of place): per
+// product g and K slab s the alt groups (k-th group of the slice, k < n_ag) whose partial an alt
+// window sums and a changed conv6 row reaches; the alt windows (index in the slice, < nw_pre) and
+// those whose tail is reached.  Every other partial of an alt window is its ref partial, bit for bit.
+struct FkAltPlan {
+  std::vector<int> grp[9][kFkSlabs];
+  std::vector<int> win, tail;
 };
 
 struct SegPlan {
@@ -112,6 +164,8 @@ struct SegPlan {
   bool fkm;                                    // FC1 as the block Karatsuba
   std::vector<std::vector<FkWin>> fk_ref, fk_alt;   // [chunk]: its windows in group order; its alt windows
   long long fk_cap;
+  bool alt_inplace;
+  std::vector<int> r6;                         // pairs: first changed conv6 row of block (entry e, phase index i) at e * n_ph + i
 
   int vw_w(int v) const { return v >= ss.n_win ? v - ss.n_win : v; }
   bool v_is_alt(int v) const { return is_alt[vw_w(v)] != 0; }
@@ -130,14 +184,18 @@ struct SegPlan {
 
   // The slice of chunk ci's group order that starts at i0: whole groups, <= fk_cap windows, and its
   // alt-group prefix (the alt groups lead the chunk's order, so they fill the first slices).
-  // Returns the refusal, or null.
+  // Out of place, an alt window counts twice (its ref and its alt FC1 output row share the slice's
+  // buffers); the first group of a slice is taken whatever it counts.  Returns the refusal, or null.
   const char* fk_slice(size_t ci, size_t i0, FkSlice& s) const {
     const std::vector<FkWin>& ws = fk_ref[ci];
-    size_t i1 = i0;
+    const bool twice = pairs && !alt_inplace && !fk_alt[ci].empty();
+    size_t i1 = i0, rows = 0;
     while (i1 < ws.size()) {
-      size_t j = i1 + 1;
-      while (j < ws.size() && fk_same_group(ws[j], ws[i1])) ++j;
-      if (j - i0 > (size_t)fk_cap && i1 > i0) break;
+      size_t j = i1, n = 0;
+      do n += twice && v_is_alt(ws[j].w) ? 2 : 1;
+      while (++j < ws.size() && fk_same_group(ws[j], ws[i1]));
+      if (rows + n > (size_t)fk_cap && i1 > i0) break;
+      rows += n;
       i1 = j;
     }
     if (i1 - i0 > (size_t)fk_cap) return "a Karatsuba FC1 window group exceeds the FC1 slice";
@@ -153,6 +211,29 @@ struct SegPlan {
       i = j - 1;
     }
     return nullptr;
+  }
+
+  // The out-of-place alt rows of slice s of chunk ci (s.n_ag > 0)
+  FkAltPlan fk_alt_plan(size_t ci, const FkSlice& s) const {
+    const std::vector<FkWin>& ws = fk_ref[ci];
+    FkAltPlan a;
+    int k = -1;
+    for (size_t i = s.i0; i < s.i0 + s.nw_pre; ++i) {
+      if (i == s.i0 || !fk_same_group(ws[i], ws[i - 1])) ++k;
+      const FkWin& w = ws[i];
+      if (!v_is_alt(w.w)) continue;
+      const int r = r6[(size_t)chunks[ci].first * n_ph + w.blk];
+      a.win.push_back((int)(i - s.i0));
+      if (fk_reach_tail(w.off6, r)) a.tail.push_back((int)(i - s.i0));
+      for (int j = 0; j < 4; ++j) {
+        const int g = kFkRole[fk_role_of(w.off6)][j];
+        for (int sb = 0; sb < kFkSlabs; ++sb) {
+          std::vector<int>& l = a.grp[g][sb];   // (k ascends: a group's alt windows are consecutive)
+          if (fk_reach(fk_group_of(w.off6), g, sb, r) && (l.empty() || l.back() != k)) l.push_back(k);
+        }
+      }
+    }
+    return a;
   }
 };
 
@@ -243,6 +324,13 @@ inline int seg_plan(const SegPlanIn& in, SegPlan& p, const char** err) {
   // (configs[2]: 14.4 k vs 16.6 k variants/s); the 200-window sweeps (5 % alt windows) gain.
   p.fkm = in.fk && !(p.pairs && 3 * p.alt_w.size() > (size_t)n_vw);
   p.fk_cap = in.fk_cap;
+  p.alt_inplace = in.alt_inplace;
+  p.r6.clear();
+  if (p.pairs)
+    for (int e = 0; e < n_ent; ++e) {
+      const int q = in.var_pos[e >= n_seg ? e - n_seg : e];
+      for (int i = 0; i < n_ph; ++i) p.r6.push_back(seg_r6(p.g, e >= p.ss.rc_ent ? L - 1 - q : q, p.ph[i]));
+    }
   p.fc_perm.clear();
   p.fk_ref.clear();
   p.fk_alt.clear();
