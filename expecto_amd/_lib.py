@@ -110,6 +110,13 @@ SIGNATURES = {
     "expecto_kmeans_lloyd": (ctypes.c_int, [c_vp, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong,
                                             ctypes.c_longlong, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp,
                                             ctypes.c_size_t, c_vp]),
+    "expecto_cluster_enrich_workspace": (ctypes.c_size_t, [ctypes.c_longlong] * 2),
+    "expecto_cluster_enrich": (ctypes.c_int, [c_vp, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, c_vp,
+                                              ctypes.c_longlong, c_vp, c_vp, c_vp, ctypes.c_longlong, c_vp, c_vp,
+                                              ctypes.c_longlong, c_vp, ctypes.c_longlong, c_vp, ctypes.c_longlong,
+                                              c_vp, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, c_vp,
+                                              c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp]),
+    "expecto_hypergeom_sf": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.c_longlong, c_vp, c_vp]),
     "expecto_last_error": (ctypes.c_char_p, []),
     "expecto_version": (ctypes.c_char_p, []),
 }

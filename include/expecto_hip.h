@@ -49,6 +49,9 @@
  *   expecto_kmeans_plusplus        the k-means++ seeding and
  *   expecto_kmeans_lloyd           the Lloyd iteration of KMeans(n_clusters=k).fit(X), batched over k and
  *                                  restarts (cluster_and_viz.py:45-58, the elbow sweep among them)
+ *   expecto_cluster_enrich         the counting of cluster_contribs_hypergeom, batched over the data, the
+ *                                  shuffled controls and the SED quartiles (cluster_analysis_with_fimo.py:126-162)
+ *   expecto_hypergeom_sf           its scipy.stats.hypergeom.sf (cluster_analysis_with_fimo.py:163)
  *   expecto_beluga_destroy         (model teardown)
  */
 #ifndef EXPECTO_HIP_H
@@ -555,6 +558,59 @@ int expecto_kmeans_lloyd(const double* X, long long n, long long d, long long ld
                          const long long* prob_host, const long long* prob, const double* tol, const double* init,
                          int* labels, double* centres, double* inertia, int* n_iter, void* workspace,
                          size_t workspace_bytes, void* stream);
+
+/* Motif-match enrichment of the top clusters (cluster_analysis_with_fimo.py:126-162: the counting of
+ * cluster_contribs_hypergeom), as P problems over one contribution matrix per call.
+ *
+ * Shared inputs (DEVICE unless said).  contrib: float64 [V, ld], ld >= C, the padding never read; it is
+ * copied to the host once, on `stream` and with a wait, and a NaN in a read element is refused.  sets:
+ * uint64 [C, W], W = ceil(M / 64): bit m of row c says that motif m is in column c's set; bits at or
+ * above M are zero.  A motif may be in several sets.  seq_ptr: int64 [S + 1], passed twice with the same
+ * contents, in HOST memory (checked: starts at 0, never decreases) and in DEVICE memory (clamped to the
+ * checked length); motif_idx: int32 [seq_ptr[S]], the match entries of sequence s at
+ * [seq_ptr[s], seq_ptr[s+1]); an entry outside [0, M) counts nowhere.  An entry may repeat.
+ *
+ * Problems: an int64 table [P, 4], passed in HOST memory (checked) and in DEVICE memory (a row that
+ * does not fit the checked sizes is passed over).  Columns:
+ *   0 permutation slot: -1 for none, else j < n_perms: column c of row v holds contrib[v, perms[j, v, c]],
+ *     perms uint16 [n_perms, V, C]; an entry >= C reads column c.  Not checked to be a permutation.
+ *   1 sid slot j < n_sids: sids int32 [n_sids, V], sids[j, v] the sequence of row v; outside [0, S): none.
+ *   2, 3 offset and count of the problem's rows in `rows` (int32 [rows_len], values in [0, V); others are
+ *     passed over).  Row lists may overlap or be shared.
+ *
+ * Per row the columns are ordered by |value| descending, equal magnitudes (+x and -x, zeros) the lower
+ * column first; rank 0 is the largest.  Outputs (DEVICE), every one a sum or minimum of integers, so
+ * independent of the launch geometry and of the order of the adds:
+ *   pos_matches int64 [P, T]  sum over rows of the row's entries whose motif is in the set at rank t
+ *   pos_motifs  int64 [P, T]  sum over rows of that set's popcount
+ *   neg         int64 [P, 2]  the same two sums for the OR of the sets at the last n_neg ranks
+ *   min_rank    int32 [P, C]  the least rank column c takes over the rows; C for a problem without rows
+ * A row without a sequence adds to the motif sums only.  workspace: at least
+ * expecto_cluster_enrich_workspace(S, C) bytes (a pure host function; 0 for a refused shape), 4-byte
+ * aligned: the matches per (sequence, column), which no problem changes, are counted once per call.
+ * Refused (EXPECTO_EINVAL, nothing launched): C outside [1, 1024], M outside [1, 32768], n_neg or T
+ * outside [1, C], ld < C, V * C or S * C >= 2^31, P > 1048576, more than 2097120 rows in a problem, a
+ * slot or row list outside its array, a null pointer, NaN in contrib.  P = 0 or V = 0 launches nothing,
+ * writes nothing and succeeds.
+ *
+ * expecto_hypergeom_sf: out[q] = P(X >= k[q]) for X hypergeometric with population M[q], n[q] marked and
+ * N[q] drawn (scipy.stats.hypergeom.sf(k - 1, M, n, N)); int64 inputs, float64 output, all DEVICE, one
+ * lane per quadruple.  NaN, as scipy's argument check gives, for M <= 0, a negative n or N, n > M or
+ * N > M.  With lo = max(0, N - (M - n)) and hi = min(n, N): 1 for k <= lo, 0 for k > hi.
+ * Otherwise the sum of the positive terms i = k .. hi: the term at max(k, mode) as the product of its
+ * 2 min(n, N) integer ratios (exponent kept apart; about 1e-13 relative at N = 1e5, where differences
+ * of lgamma give 1e-9), its neighbours by the ratio (n-i)(N-i) / ((i+1)(M-n-N+i+1)) upwards and its
+ * inverse downwards, each direction until a term no longer changes the sum.  count = 0 succeeds without a launch. */
+size_t expecto_cluster_enrich_workspace(long long S, long long C);
+int expecto_cluster_enrich(const double* contrib, long long V, long long C, long long ld,
+                           const unsigned long long* sets, long long M, const long long* seq_ptr_host,
+                           const long long* seq_ptr, const int* motif_idx, long long S, const long long* prob_host,
+                           const long long* prob, long long P, const unsigned short* perms, long long n_perms,
+                           const int* sids, long long n_sids, const int* rows, long long rows_len, long long n_neg,
+                           long long T, long long* pos_matches, long long* pos_motifs, long long* neg, int* min_rank,
+                           void* workspace, size_t workspace_bytes, void* stream);
+int expecto_hypergeom_sf(const long long* k, const long long* M, const long long* n, const long long* N,
+                         long long count, double* out, void* stream);
 
 const char* expecto_last_error(void);
 const char* expecto_version(void);
