@@ -117,6 +117,11 @@ SIGNATURES = {
                                               c_vp, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, c_vp,
                                               c_vp, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp]),
     "expecto_hypergeom_sf": (ctypes.c_int, [c_vp, c_vp, c_vp, c_vp, ctypes.c_longlong, c_vp, c_vp]),
+    "expecto_pwm_pvalues": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_longlong, c_vp, c_vp, c_vp, ctypes.c_longlong,
+                                           c_vp]),
+    "expecto_pwm_scan": (ctypes.c_int, [c_vp, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, c_vp, c_vp, c_vp,
+                                        c_vp, ctypes.c_longlong, c_vp, c_vp, ctypes.c_longlong, c_vp, c_vp, c_vp, c_vp,
+                                        c_vp]),
     "expecto_last_error": (ctypes.c_char_p, []),
     "expecto_version": (ctypes.c_char_p, []),
 }

@@ -8,6 +8,10 @@ the variant (a FIMO text table)?  One hypergeometric p-value per "top cluster in
         [--downstream_bp 30] [--pval_match_threshold 1e-4] [--n_neg_clusters 20] [--n_permutations 1] \\
         [-o temp_cluster_analysis_with_fimo]
 
+Without a FIMO table: ``--motif_file M.meme --vcf_file V [--hg19_fasta F] [--bgfile nrdb] [--motif-pseudo 0.1]
+[--seq-batch 8192]`` in place of ``--fimo_out_file`` scans the motifs over the variants' flanks on the device
+(``expecto_amd.query_fimo_for_predictions``: :func:`scan_matches`); the matches never become text.
+
 Reading and filtering are the reference's pandas calls (cluster_analysis_with_fimo.py:31-58).  The
 triple loop of ``cluster_contribs_hypergeom`` is ``expecto_cluster_enrich`` (include/expecto_hip.h): the
 seven problems of a run (the data, shuffled clusters, shuffled variants, four SED quartiles) are one
@@ -51,8 +55,8 @@ class Inputs(NamedTuple):
     columns: list              # their names
     sets: list                 # per column the set of its motif indices
     motifs: list               # motif names; the index is the motif's bit
-    matches: list              # per sequence the motif indices of its filtered FIMO rows
-    sequences: list            # distinct FIMO sequence names
+    matches: object            # per sequence the motif indices of its filtered FIMO rows (--motif_file: their CSR pair)
+    sequences: list            # distinct FIMO sequence names (--motif_file: the variants' IDs)
     sid: np.ndarray            # int32 [V]: the row's sequence, -1 without one
     sed: np.ndarray            # float64 [V]: the column the quartiles are cut on
     n_cluster_rows: int        # rows of the cluster table, cluster_-1 among them
@@ -129,17 +133,27 @@ def load(args, rs=None) -> Inputs:
     if args.rank_int:
         sed = rank_int(sed, cluster_contribs_df["gene"].to_numpy(), rs if rs is not None else np.random.RandomState(1))
 
-    fimo_df = pd.read_table(args.fimo_out_file, sep='\t', names=FIMO_COLUMNS, comment='#')
     per_cluster = {str(k): str(v).split(",") for k, v in rsat_clusters_df[1].items()}
     placed = set(sum(rsat_clusters_df[1][:-1].str.split(",").tolist(), []))          # skip cluster_-1
-    n_motifs_total = len(set(fimo_df["motif_alt_id"]))
-    if n_motifs_total != len(placed):
-        raise ValueError(f"{args.fimo_out_file} names {n_motifs_total} motifs, the clusters of "
-                         f"{args.rsat_clusters_file} hold {len(placed)} (the reference asserts that they agree)")
     missing = [c for c in columns if c not in per_cluster]
-    if missing:
-        raise ValueError(f"{args.rsat_clusters_file} has no row for {missing[0]} "
-                         f"(and {len(missing) - 1} more columns of {args.cluster_contribs_file})")
+    motifs = sorted(set(sum(per_cluster.values(), [])))
+    bit = {m: i for i, m in enumerate(motifs)}
+    sets = None if missing else [{bit[m] for m in per_cluster[c]} for c in columns]
+
+    def agree(source, n_motifs_total):
+        if n_motifs_total != len(placed):
+            raise ValueError(f"{source} names {n_motifs_total} motifs, the clusters of "
+                             f"{args.rsat_clusters_file} hold {len(placed)} (the reference asserts that they agree)")
+        if missing:
+            raise ValueError(f"{args.rsat_clusters_file} has no row for {missing[0]} "
+                             f"(and {len(missing) - 1} more columns of {args.cluster_contribs_file})")
+
+    if getattr(args, "fimo_out_file", None) is None:
+        matches, sequences, sid = scan_matches(args, bit, rsids, agree)
+        return Inputs(contrib, columns, sets, motifs, matches, sequences, sid, sed, int(rsat_clusters_df.shape[0]))
+
+    fimo_df = pd.read_table(args.fimo_out_file, sep='\t', names=FIMO_COLUMNS, comment='#')
+    agree(args.fimo_out_file, len(set(fimo_df["motif_alt_id"])))
 
     # subset to motifs within range of the variant, the most significant match per motif and variant, threshold
     fimo_df = fimo_df[(fimo_df["start"] <= (args.upstream_bp + 1)) & (fimo_df["stop"] >= (args.upstream_bp + 1))]
@@ -147,9 +161,6 @@ def load(args, rs=None) -> Inputs:
                                                                 keep="first")
     fimo_df = fimo_df[fimo_df["p-value"] < args.pval_match_threshold]
 
-    motifs = sorted(set(sum(per_cluster.values(), [])))
-    bit = {m: i for i, m in enumerate(motifs)}
-    sets = [{bit[m] for m in per_cluster[c]} for c in columns]
     sequences, where, matches = [], {}, []
     for name, motif in zip(fimo_df["sequence_name"].tolist(), fimo_df["motif_alt_id"].tolist()):
         if name not in where:
@@ -160,6 +171,37 @@ def load(args, rs=None) -> Inputs:
             matches[where[name]].append(bit[motif])
     sid = np.array([where.get(r, -1) for r in rsids], np.int32)
     return Inputs(contrib, columns, sets, motifs, matches, sequences, sid, sed, int(rsat_clusters_df.shape[0]))
+
+
+def scan_matches(args, bit, rsids, agree):
+    """The ``--motif_file`` route: the motifs of a MEME file scanned on the device over the flanks
+    ``POS - upstream_bp .. POS + downstream_bp`` of the variants of ``--vcf_file``
+    (query_fimo_for_predictions: ``scan`` + ``matches_csr``); no FIMO table.  A match is the best window
+    over the variant with p < ``--pval_match_threshold``, the filter of the other route.  Returns the CSR
+    pair of the matches in ``bit`` numbering, the sequence names and the rows' sequences."""
+    from . import query_fimo_for_predictions as q
+    from .genome import open_genome
+
+    meme = q.read_meme(args.motif_file)
+    agree(args.motif_file, len(set(meme.alt_ids)))
+    bg = q.background(args.bgfile, meme)
+    motifs = q.Motifs.from_meme(meme, bg, args.motif_pseudo)
+    names, _, codes = q.flanks(q.read_vcf(args.vcf_file), open_genome(args.hg19_fasta), args.upstream_bp,
+                               args.downstream_bp)
+    where = {n: i for i, n in enumerate(names)}
+    if len(where) != len(names):
+        raise ValueError(f"{args.vcf_file}: a variant ID appears twice; the rows of {args.cluster_contribs_file} find "
+                         "their sequence by it")
+    tables = q.pvalue_tables(motifs, bg)
+    motif_map = np.array([bit.get(a, -1) for a in motifs.alt_ids], np.int64)
+    ptrs, idxs = [np.zeros(1, np.int64)], [np.zeros(0, np.int32)]
+    for s0 in range(0, len(names), max(1, args.seq_batch)):
+        res = q.scan(codes[s0:s0 + max(1, args.seq_batch)], args.upstream_bp, motifs, tables)
+        ptr, idx = q.matches_csr(res[3], args.pval_match_threshold, motif_map)
+        ptrs.append(ptr[1:] + ptrs[-1][-1])
+        idxs.append(idx)
+    sid = np.array([where.get(r, -1) for r in rsids], np.int32)
+    return (np.concatenate(ptrs), np.concatenate(idxs).astype(np.int32)), names, sid
 
 
 # ---- problems ---------------------------------------------------------------------------------
@@ -372,7 +414,13 @@ def build_parser():
                                      description='Analyze fimo results with cluster contribs')
     parser.add_argument("--cluster_contribs_file", required=True)
     parser.add_argument("--rsat_clusters_file", required=True)
-    parser.add_argument("--fimo_out_file", required=True)
+    parser.add_argument("--fimo_out_file", default=None, help="a FIMO text table; or give --motif_file and --vcf_file")
+    parser.add_argument("--motif_file", default=None, help="a MEME file: its motifs are scanned on the device")
+    parser.add_argument("--vcf_file", default=None, help="with --motif_file: the variants")
+    parser.add_argument("--hg19_fasta", default="resources/hg19.fa")
+    parser.add_argument("--bgfile", default="nrdb", help="nrdb, motif-file, uniform, or a file of 'A 0.29' lines")
+    parser.add_argument("--motif-pseudo", dest="motif_pseudo", type=float, default=0.1)
+    parser.add_argument("--seq-batch", dest="seq_batch", type=int, default=8192, help="sequences per device call")
     parser.add_argument("--rank_int", default=False, action="store_true",
                         help="use rank-based inverse normal transformation for SED scores")
     parser.add_argument("--upstream_bp", type=int, default=30)
@@ -402,6 +450,8 @@ def run(args, out=None, timings=None):
         raise ValueError("--n_neg_clusters must be at least 1")
     if args.n_permutations < 1:
         raise ValueError("--n_permutations must be at least 1")
+    if route_error(args):
+        raise ValueError(route_error(args))
     os.makedirs(args.out_dir, exist_ok=True)
     rs = np.random.RandomState(1)
     inp = load(args, rs)
@@ -418,7 +468,7 @@ def run(args, out=None, timings=None):
     first = next(shuffles)
     draw_s = time.perf_counter() - t0
     set_bits = bitsets(inp.sets, len(inp.motifs))
-    match_csr = csr(inp.matches)
+    match_csr = inp.matches if isinstance(inp.matches, tuple) else csr(inp.matches)
 
     null = None
     if T >= 1 and V >= 1:
@@ -467,8 +517,24 @@ def run(args, out=None, timings=None):
     return res, null
 
 
+def route_error(args):
+    """Why the arguments name no single source of matches, or None."""
+    table, scan = getattr(args, "fimo_out_file", None), getattr(args, "motif_file", None)
+    if table is not None and scan is not None:
+        return "give --fimo_out_file or --motif_file, not both"
+    if table is None and scan is None:
+        return "give --fimo_out_file, or --motif_file with --vcf_file"
+    if scan is not None and getattr(args, "vcf_file", None) is None:
+        return "--motif_file needs --vcf_file"
+    return None
+
+
 def main(argv=None):
-    return run(build_parser().parse_args(argv))
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if route_error(args):
+        parser.error(route_error(args))
+    return run(args)
 
 
 if __name__ == "__main__":

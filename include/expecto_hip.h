@@ -52,6 +52,9 @@
  *   expecto_cluster_enrich         the counting of cluster_contribs_hypergeom, batched over the data, the
  *                                  shuffled controls and the SED quartiles (cluster_analysis_with_fimo.py:126-162)
  *   expecto_hypergeom_sf           its scipy.stats.hypergeom.sf (cluster_analysis_with_fimo.py:163)
+ *   expecto_pwm_pvalues            the score-to-p-value tables of `fimo` (query_fimo_for_predictions.py:45) and
+ *   expecto_pwm_scan               its matches, reduced to the best one that overlaps the variant per motif
+ *                                  and sequence (query_fimo_for_predictions.py:53-57)
  *   expecto_beluga_destroy         (model teardown)
  */
 #ifndef EXPECTO_HIP_H
@@ -611,6 +614,49 @@ int expecto_cluster_enrich(const double* contrib, long long V, long long C, long
                            void* workspace, size_t workspace_bytes, void* stream);
 int expecto_hypergeom_sf(const long long* k, const long long* M, const long long* n, const long long* N,
                          long long count, double* out, void* stream);
+
+/* Motif scan of short sequences with FIMO's scoring model (query_fimo_for_predictions.py:43-57), as far as
+ * it is documented (Grant, Bailey, Noble 2011); agreement with the `fimo` binary has not been measured.
+ *
+ * Motifs: pssm int16 [col_ptr[M], 4] (DEVICE), the scaled log-odds entries in 0..100, a row per motif
+ * column, the four entries in base-code order (0=A 1=G 2=C 3=T); col_ptr int32 [M + 1], passed twice with
+ * the same contents, in HOST memory (checked: starts at 0, widths in [1, 64]) and in DEVICE memory (a
+ * motif that does not fit the checked sizes is passed over).  Table of motif m: 100 w + 1 doubles at
+ * tables[pv_ptr[m]], pv_ptr[m] = 100 col_ptr[m] + m: the tables lie back to back.
+ *
+ * expecto_pwm_pvalues: bg_host float64 [4] (HOST, code order, each in (0, 1)).  Writes pv_ptr int64
+ * [M + 1] and the tables (both DEVICE): pv[j] = P(score >= j) of a sequence of w independent letters drawn
+ * from bg.  All float64, products and sums rounded separately (no FMA), one workgroup per motif:
+ *   pdf = [1.0]; per column i = 0..w-1: new[0..100(i+1)] = +0.0, then for k ascending and the letters in
+ *   alphabet order (A C G T) new[k + s[i][a]] += pdf[k] * bg[a].  The kernel gathers: new[j] is +0.0 plus
+ *   its up to four terms in that same order (entry descending, then alphabet order).
+ *   pv[100 w] = pdf[100 w], pv[j] = pv[j + 1] + pdf[j] downwards, one chain; then pv = min(pv, 1.0), and
+ *   pv[0] = 1.0: every score is >= 0, and the clip alone leaves a chain that ends a few ulp below 1 there.
+ * pssm is copied to the host once, on `stream` and with a wait, for the entry check.  Refused
+ * (EXPECTO_EINVAL, nothing launched or written): a width outside [1, 64], a decreasing col_ptr, an entry
+ * outside 0..100, tables_len < 100 col_ptr[M] + M, a background frequency outside (0, 1), a null pointer.
+ * M = 0 succeeds without a launch.
+ *
+ * expecto_pwm_scan: codes uint8 [S, ld] (DEVICE), ld >= L, columns at or above L never read; a code >= 4
+ * is no base.  overlap int32 [S] (DEVICE): c >= 0 keeps the windows that cover position c (0-based), a
+ * negative c all windows.  Window start p of a motif of width w is admissible when 0 <= p, p + w <= L,
+ * p <= c <= p + w - 1 (c >= 0), and no code in the window is >= 4.  Scores are integer sums:
+ *   '+': sum_i s[i][seq[p + i]];   '-': sum_i s[w-1-i][3 - seq[p + i]] (the reverse-complement motif read
+ *   on the given strand).
+ * Outputs (DEVICE, [S, M] row-major), the maximum score, equal scores to the smaller p, then to '+':
+ *   score int32 (-1: no admissible window), start int32 (0-based p, or -1), strand uint8 (0 '+', 1 '-'),
+ *   pvalue float64 = tables[pv_ptr[m] + score] (NaN without a window): the one non-integer step, a lookup;
+ *   both strands read the forward matrix's table.
+ * Plain vector stores, no atomics: the bits depend on nothing but the pair's own inputs.  A workgroup takes
+ * 64 sequences x 16 motifs.  Refused: L outside [1, 256], ld < L, a width outside [1, 64], a decreasing
+ * col_ptr, M > 1048560, tables_len < 100 col_ptr[M] + M, a null pointer.  S = 0 or M = 0 succeeds without a
+ * launch. */
+int expecto_pwm_pvalues(const short* pssm, const int* col_ptr_host, const int* col_ptr, long long M,
+                        const double* bg_host, double* tables, long long* pv_ptr, long long tables_len, void* stream);
+int expecto_pwm_scan(const unsigned char* codes, long long S, long long L, long long ld, const int* overlap,
+                     const short* pssm, const int* col_ptr_host, const int* col_ptr, long long M, const double* tables,
+                     const long long* pv_ptr, long long tables_len, int* score, int* start, unsigned char* strand,
+                     double* pvalue, void* stream);
 
 const char* expecto_last_error(void);
 const char* expecto_version(void);
