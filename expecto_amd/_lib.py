@@ -122,6 +122,12 @@ SIGNATURES = {
     "expecto_pwm_scan": (ctypes.c_int, [c_vp, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, c_vp, c_vp, c_vp,
                                         c_vp, ctypes.c_longlong, c_vp, c_vp, ctypes.c_longlong, c_vp, c_vp, c_vp, c_vp,
                                         c_vp]),
+    "expecto_rank2_f32": (ctypes.c_int, [c_vp, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, c_vp, c_vp]),
+    "expecto_rank2_f64": (ctypes.c_int, [c_vp, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, c_vp, c_vp]),
+    "expecto_model_metrics": (ctypes.c_int, [c_vp, ctypes.c_longlong, c_vp, ctypes.c_longlong, c_vp, c_vp,
+                                             ctypes.c_int, ctypes.c_int, c_vp, c_vp]),
+    "expecto_bootstrap_coef_stats": (ctypes.c_int, [c_vp, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, c_vp, c_vp,
+                                                    c_vp, c_vp, c_vp, c_vp]),
     "expecto_last_error": (ctypes.c_char_p, []),
     "expecto_version": (ctypes.c_char_p, []),
 }

@@ -19,6 +19,12 @@ features.  ``--n_bootstrap K --seed S`` folds in ``train_bootstrap.py``: replica
 the draw of ``train_bootstrap.py --seed S``) and trains on the draw counts as row weights, not
 on a gathered copy; its files carry ``.boot{k}`` ahead of the extension.  ``--l1`` is passed on
 as ``alpha`` (the reference parses it and then trains with ``alpha: 0``; the default is 0).
+``--holdout CHR [CHR ...]`` takes those chromosomes out of the training rows as well
+(``train_susztak.py:117-120`` holds out chr7).  ``--metrics`` scores every model of a batch on the
+device (:mod:`expecto_amd.metrics`: Pearson r, Spearman r and R2 on its unweighted train rows and
+on its chr8 rows, labels in float64) and writes ``<output_dir>/metrics/metrics.h5`` (the datasets
+of ``train_susztak.py:177-181`` plus ``spearmanr_trains`` / ``spearmanr_valids``, in model order)
+and ``metrics.tsv``.  Both are off by default, and then nothing changes.
 
 Left out: the scatter plots (``train.py:161-184``), ``--kidney_genes_only`` and
 ``--match_with_basenji2`` (the latter reads a hard-coded path of its author's machine).
@@ -42,6 +48,18 @@ def build_parser():
     p = argparse.ArgumentParser(description='Process some integers.')
     p.add_argument('--targetIndex', action="store", dest="targetIndex", nargs='+', required=True,
                    help="column(s) of expFile to train on, or 'all'")
+    add_reference_arguments(p)
+    p.add_argument('--n_bootstrap', type=int, default=0, help="bootstrap replicates per target (0: none)")
+    p.add_argument('--seed', action="store", dest="seed", type=int, default=0)
+    p.add_argument('--holdout', nargs='+', default=[], metavar='CHR',
+                   help="chromosomes taken out of the training rows (train_susztak.py holds out chr7)")
+    p.add_argument('--metrics', action='store_true', default=False,
+                   help="score every model on its train and test rows; write metrics/metrics.h5 and metrics.tsv")
+    return p
+
+
+def add_reference_arguments(p):
+    """The arguments train.py:27-77 and train_susztak.py:28-69 share."""
     p.add_argument('--expFile', action="store", dest="expFile")
     p.add_argument('--belugaFeatures', action="store", dest="belugaFeatures", help="tsv file denoting Beluga features")
     p.add_argument('--inputFile', action="store", dest="inputFile", default='./resources/Xreducedall.2002.npy')
@@ -62,9 +80,6 @@ def build_parser():
     p.add_argument('--intersect_with_lambert', action='store_true', dest='intersect_with_lambert', default=False)
     p.add_argument('--no_pol2', action='store_true', dest='no_pol2', default=False)
     p.add_argument('--output_dir', type=str, default='temp_expecto_model')
-    p.add_argument('--n_bootstrap', type=int, default=0, help="bootstrap replicates per target (0: none)")
-    p.add_argument('--seed', action="store", dest="seed", type=int, default=0)
-    return p
 
 
 def gene_filter(geneanno: pd.DataFrame, filter_str: str) -> np.ndarray:
@@ -78,13 +93,15 @@ def gene_filter(geneanno: pd.DataFrame, filter_str: str) -> np.ndarray:
     raise ValueError('filterStr has to be one of all, pc, and lincRNA')
 
 
-def select_rows(geneanno: pd.DataFrame, expr: pd.Series, filter_str: str, pseudocount: float):
+def select_rows(geneanno: pd.DataFrame, expr: pd.Series, filter_str: str, pseudocount: float, holdout=()):
     """Boolean (train, test) masks over the genes for one expression column (train.py:86-100,
-    :127-132)."""
+    :127-132); ``holdout`` chromosomes leave the training rows as well (train_susztak.py:117-120)."""
     with np.errstate(divide='ignore', invalid='ignore'):
         filt = gene_filter(geneanno, filter_str) * np.isfinite(np.asarray(np.log(expr + pseudocount)))
     trainind = np.asarray(geneanno['seqnames'] != 'chrX') * np.asarray(
         geneanno['seqnames'] != 'chrY') * np.asarray(geneanno['seqnames'] != 'chr8')
+    for c in holdout:
+        trainind = trainind * np.asarray(geneanno['seqnames'] != c)
     testind = np.asarray(geneanno['seqnames'] == 'chr8')
     return np.asarray(trainind * filt, dtype=bool), np.asarray(testind * filt, dtype=bool)
 
@@ -112,10 +129,34 @@ def spearman_line(ypred, ytrue) -> str:
         return f"SignificanceResult(statistic={rho}, pvalue=nan)"
 
 
-def run(args) -> list:
+METRIC_NAMES = ('pearsonr_trains', 'pearsonr_valids', 'spearmanr_trains', 'spearmanr_valids', 'r2_trains',
+                'r2_valids')
+
+
+def write_metrics(output_dir: str, results: list) -> None:
+    """``<output_dir>/metrics/metrics.h5`` with the four datasets of train_susztak.py:177-181 and the two
+    Spearman ones, float64 in model order, and ``metrics.tsv`` with the same figures per model."""
+    from . import h5
+
+    metrics_dir = f'{output_dir}/metrics'
+    os.makedirs(metrics_dir, exist_ok=True)
+    cols = {k: np.array([r["metrics"][k] for r in results], dtype=np.float64) for k in METRIC_NAMES}
+    h5.write(f'{metrics_dir}/metrics.h5', cols)
+    with open(f'{metrics_dir}/metrics.tsv', 'w') as f:
+        f.write('\t'.join(('name', 'boot') + METRIC_NAMES) + '\n')
+        for m, r in enumerate(results):
+            f.write('\t'.join([str(r["name"]), '' if r["boot"] is None else str(r["boot"])] +
+                              ['%.17g' % cols[k][m] for k in METRIC_NAMES]) + '\n')
+
+
+def run(args, model_dir=None) -> list:
     """Train every requested model; returns one dict per model (name, boot, model, history,
-    save, dump) in the order their lines were printed."""
+    save, dump; with ``--metrics`` also metrics) in the order their lines were printed.  The model
+    files go to ``model_dir`` (default: ``args.output_dir``)."""
+    holdout, want_metrics = getattr(args, 'holdout', None) or [], bool(getattr(args, 'metrics', False))
+    model_dir = args.output_dir if model_dir is None else model_dir
     os.makedirs(args.output_dir, exist_ok=True)
+    os.makedirs(model_dir, exist_ok=True)
     X = np.load(args.inputFile)
     geneanno = pd.read_csv(args.annoFile)
     geneexp = pd.read_csv(args.expFile)
@@ -135,7 +176,7 @@ def run(args) -> list:
     # targets with the same row selection share one device copy of the features and one batch
     groups = {}
     for ti in targets:
-        tr, te = select_rows(geneanno, geneexp.iloc[:, ti], args.filterStr, args.pseudocount)
+        tr, te = select_rows(geneanno, geneexp.iloc[:, ti], args.filterStr, args.pseudocount, holdout)
         groups.setdefault((tr.tobytes(), te.tobytes()), (tr, te, []))[2].append(ti)
 
     results = []
@@ -153,7 +194,12 @@ def run(args) -> list:
         yte = np.stack([j[4] for j in jobs])
         models, history = train(Xtr, ytr, wtr, num_round=args.num_round, eta=args.eta, lambda_=args.l2,
                                 alpha=args.l1, base_score=args.base_score, evals=[(Xte, yte)])
-        ypred = predict_cols(Xte, models).cpu().numpy()
+        ypred_dev = predict_cols(Xte, models)
+        ypred = ypred_dev.cpu().numpy()
+        if want_metrics:
+            # labels in float64 as the reference hands them to scipy; train-set figures are unweighted
+            from .metrics import model_metrics
+            scores = np.concatenate([model_metrics(predict_cols(Xtr, models), ytr), model_metrics(ypred_dev, yte)], 1)
         for m, (ti, k, _, _, ytrue) in enumerate(jobs):
             name = geneexp.columns[ti]
             print(f"Cell type: {name}" + ("" if k is None else f" (bootstrap {k})"))
@@ -164,12 +210,18 @@ def run(args) -> list:
             if args.evalFile != '':
                 path = args.evalFile if len(jobs) == 1 and len(groups) == 1 else f"{args.evalFile}.{name}{tag}"
                 pd.DataFrame({'pred': ypred[m], 'target': ytrue}).to_csv(path)
-            stem = (f'{args.output_dir}/expecto_{args.filterStr}.pseudocount{args.pseudocount}.lambda{args.l2}'
+            stem = (f'{model_dir}/expecto_{args.filterStr}.pseudocount{args.pseudocount}.lambda{args.l2}'
                     f'.round{args.num_round}.basescore{args.base_score}.{name}{tag}')
             models[m].save_legacy(stem + '.save')
             models[m].save_dump(stem + '.dump')
             results.append({"name": name, "boot": k, "model": models[m], "history": history[m],
                             "save": stem + '.save', "dump": stem + '.dump'})
+            if want_metrics:
+                pt, st, rt, pv, sv, rv = (float(v) for v in scores[m])
+                results[-1]["metrics"] = {'pearsonr_trains': pt, 'pearsonr_valids': pv, 'spearmanr_trains': st,
+                                          'spearmanr_valids': sv, 'r2_trains': rt, 'r2_valids': rv}
+    if want_metrics:
+        write_metrics(args.output_dir, results)
     return results
 
 

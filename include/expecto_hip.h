@@ -55,6 +55,12 @@
  *   expecto_pwm_pvalues            the score-to-p-value tables of `fimo` (query_fimo_for_predictions.py:45) and
  *   expecto_pwm_scan               its matches, reduced to the best one that overlaps the variant per motif
  *                                  and sequence (query_fimo_for_predictions.py:53-57)
+ *   expecto_rank2_f32 / _f64       scipy's rankdata inside spearmanr (train.py:150,163; train_bootstrap.py:110,124)
+ *   expecto_model_metrics          pearsonr, spearmanr and r2_score of a model's predictions
+ *                                  (train_susztak.py:153-154; train.py:163,171-172; train_bootstrap.py:124,132-133;
+ *                                   geuvadis_predict_consensus.py:254-256 and its _for_top_eqtls copy)
+ *   expecto_bootstrap_coef_stats   np.std(ddof=1) / np.mean over the bootstrap models, the z-score and the
+ *                                  coefficient of variation (plot_bootstrapped_coefficients.py:56,64,75)
  *   expecto_beluga_destroy         (model teardown)
  */
 #ifndef EXPECTO_HIP_H
@@ -657,6 +663,46 @@ int expecto_pwm_scan(const unsigned char* codes, long long S, long long L, long 
                      const short* pssm, const int* col_ptr_host, const int* col_ptr, long long M, const double* tables,
                      const long long* pv_ptr, long long tables_len, int* score, int* start, unsigned char* strand,
                      double* pvalue, void* stream);
+
+/* Scores of trained models and statistics of a bootstrap batch (train_susztak.py:146-181,
+ * plot_bootstrapped_coefficients.py:52-76).  All pointers are DEVICE memory, strides are in elements, and a
+ * refused call (EXPECTO_EINVAL) launches and writes nothing.
+ *
+ * expecto_rank2_f32 / _f64: x holds P rows of n values, row p at x + p*stride; out int32 [P, n] (contiguous)
+ * receives out[p, i] = 2 * #{j : x_j < x_i} + #{j : x_j == x_i} + 1, twice scipy's rankdata(method='average')
+ * as an exact integer.  The ranks are counted, not sorted: one thread owns one i, the row streams through
+ * LDS, the grid is (ceil(n / 256), P).  The comparisons are IEEE < and ==: -0.0 ties with 0.0, and a NaN
+ * compares false with everything (its own doubled rank is 1, and it does not move the others').
+ * 0 <= n <= EXPECTO_METRICS_MAX_ROWS, 0 <= P <= 65535; n = 0 or P = 0 succeeds without a launch.
+ *
+ * expecto_model_metrics: out float64 [P, 3] = (pearson, spearman, r2) of model p's predictions
+ * pred + p*pred_stride (float32 [n]) against the labels y + p*y_stride (float64 [n]; y_stride == 0: every
+ * model shares one label row).  rank_pred int32 [P, n] and rank_y int32 [P, n] (or [n] when y_stride == 0)
+ * are the doubled ranks of the same rows from expecto_rank2_*.  One workgroup of 256 threads per model.
+ *   spearman = double(n Sab - Sa Sb) / sqrt(double(n Saa - Sa^2) * double(n Sbb - Sb^2)) from exact int64 sums
+ *   of the doubled ranks; a doubled rank is at most 2n, so every term is at most 4 n^4 = 2^62 at n = 32768
+ *   (below even the cruder bound n^2 (2n+1)^2 ~ 4.6e18 < 2^63).  A zero denominator gives NaN, as scipy does
+ *   for a constant input.
+ *   pearson and r2 in float64, two passes, pred widened exactly, no FMA.  Every sum: thread t adds elements
+ *   t, t+256, ... in ascending order onto +0.0, then the 256 partials fold by p[i] = p[i] + p[i+w] for i < w,
+ *   w = 128 ... 1.  mx = Sx / double(n), my likewise; sxy = S (x-mx)(y-my), sxx, syy, ssr = S (y-x)^2;
+ *   pearson = sxy / sqrt(sxx * syy) clipped to [-1, 1]; r2 = 1 - ssr / syy, and for syy == 0 sklearn's
+ *   force_finite: 1.0 if ssr == 0 else 0.0.
+ * A NaN anywhere in a model's pred or y makes its three outputs NaN.  2 <= n <= EXPECTO_METRICS_MAX_ROWS,
+ * P >= 0 (P = 0 succeeds without a launch).
+ *
+ * expecto_bootstrap_coef_stats: W float64 [B, F] row-major with row stride ld >= F, the coefficients of B
+ * bootstrap models; w_main float64 [F], the main model's.  One thread per coefficient walks the models in
+ * ascending order (numpy's order for an axis=0 reduction), no FMA:
+ *   mean = S w / B; se = sqrt(S (w - mean)^2 / (B - 1)); z = w_main / se; cv = se / |mean|   (float64 [F] each)
+ * with IEEE division by zero kept (inf or NaN, as numpy gives).  2 <= B <= 4096, F >= 0. */
+#define EXPECTO_METRICS_MAX_ROWS 32768
+int expecto_rank2_f32(const float* x, long long stride, int n, int P, int* out, void* stream);
+int expecto_rank2_f64(const double* x, long long stride, int n, int P, int* out, void* stream);
+int expecto_model_metrics(const float* pred, long long pred_stride, const double* y, long long y_stride,
+                          const int* rank_pred, const int* rank_y, int n, int P, double* out, void* stream);
+int expecto_bootstrap_coef_stats(const double* W, long long ld, int B, int F, const double* w_main, double* mean,
+                                 double* se, double* z, double* cv, void* stream);
 
 const char* expecto_last_error(void);
 const char* expecto_version(void);
