@@ -3,7 +3,8 @@
 ``predict_by_cluster --feature_clusters_df`` reads.
 
     python -m expecto_amd.cluster_and_viz <svd_transform_dir> --belugaFeatures features.tsv [ablation flags] \\
-        [-o temp_cluster_and_viz] [--n_pcs 20] [--n_clusters 30] [--n_init 1] [--seed 0] [--elbow K_MIN K_MAX STEP]
+        [-o temp_cluster_and_viz] [--n_pcs 20] [--n_clusters 30] [--n_init 1] [--seed 0] [--elbow K_MIN K_MAX STEP] \\
+        [--tsne] [--tsne_perplexity 30] [--tsne_iter 1000] [--tsne_init pca|random]
 
 The reference runs ``KMeans(n_clusters=30)`` after ``np.random.seed(0)`` on the first 20 coordinates.
 Here the seeding (sklearn's greedy k-means++) and the Lloyd iteration run on the device
@@ -13,9 +14,15 @@ Here the seeding (sklearn's greedy k-means++) and the Lloyd iteration run on the
 sweep the reference has commented out (``for k in range(2, 200, 5)``): every ``(k, restart)`` is one
 problem of a single seeding call and a single Lloyd call.
 
+``--tsne`` adds the reference's picture, ``TSNE(n_components=2, random_state=0).fit_transform(X)`` coloured
+by cluster: exact t-SNE on the device (:func:`tsne`; ``expecto_tsne_affinities``, ``expecto_tsne_descend``)
+where sklearn defaults to the Barnes-Hut approximation, written as ``tsne_embedding.tsv``, ``tsne.json``
+and, if matplotlib is installed, ``tsne.png`` (saved, never shown).  Off by default.
+
 Differences from the reference, on purpose:
 * float64 arithmetic on the file's float32 values (sklearn computes in float32 through BLAS there);
-* no t-SNE and no scatter plot: a picture that nothing downstream reads;
+* the t-SNE picture is opt-in (``--tsne``), exact rather than Barnes-Hut, starts from a full SVD's
+  principal scores kept in float64 (sklearn: a randomized PCA cast to float32), and goes to files;
 * ``--intersect_with_lambert`` and ``--no_pol2`` of cluster_utils are accepted, as in ``svd.py``;
 * a ``.npy`` whose row count differs from the number of kept marks is refused with a message (the
   reference dies with a pandas length error).
@@ -191,6 +198,175 @@ def kmeans(X, k: int, n_init: int = 1, seed=0, max_iter: int = 300, tol: float =
     return kmeans_sweep(X, [k], n_init=n_init, seed=seed, max_iter=max_iter, tol=tol, device=device)[0]
 
 
+# ---- t-SNE -----------------------------------------------------------------------------------
+
+class TSNEResult(NamedTuple):
+    embedding: np.ndarray     # float64 [n, 2]
+    kl_divergence: float      # of the last iteration run
+    n_iter: int               # iterations run (sklearn's n_iter_ is the last one's index, one less)
+    beta: np.ndarray          # float64 [n]: the precision 1 / (2 sigma_i^2) the perplexity search found per point
+
+
+def _tsne_checked(X, perplexity):
+    X = np.array(X, dtype=np.float64, order='C')
+    if X.ndim != 2:
+        raise ValueError(f"tsne: X must be 2-D, got shape {X.shape}")
+    if not np.isfinite(X).all():
+        raise ValueError("tsne: X contains NaN or infinity")
+    n, d = X.shape
+    if not (2 <= n <= MAX_N and 1 <= d <= MAX_D):
+        raise ValueError(f"tsne: X has shape {X.shape}; supported are 2..{MAX_N} points of 1..{MAX_D} dimensions")
+    perplexity = float(perplexity)
+    if not 0.0 < perplexity < n:
+        raise ValueError(f"tsne: perplexity = {perplexity} outside (0, n) with n = {n}")
+    return X, perplexity
+
+
+def tsne_init(X, init='pca', seed=0):
+    """The initial embedding, float64 [n, 2], on the host.  ``'pca'``: the first two principal scores from
+    numpy's SVD of the centred X with sklearn's sign convention (``svd_flip`` decided on v), scaled to a
+    standard deviation of 1e-4 along the first; ``'random'``: ``1e-4 * RandomState(seed).standard_normal``;
+    an [n, 2] array is taken as given."""
+    X = np.asarray(X, np.float64)
+    n = X.shape[0]
+    if isinstance(init, str):
+        if init == 'random':
+            return 1e-4 * np.random.RandomState(seed).standard_normal((n, 2))
+        if init != 'pca':
+            raise ValueError(f"tsne: init = {init!r}; supported are 'pca', 'random' and an [n, 2] array")
+        if X.shape[1] < 2:
+            raise ValueError("tsne: init='pca' needs at least 2 dimensions")
+        U, S, Vt = np.linalg.svd(X - X.mean(axis=0), full_matrices=False)
+        signs = np.sign(Vt[np.arange(Vt.shape[0]), np.argmax(np.abs(Vt), axis=1)])
+        Y = (U * signs)[:, :2] * S[:2]
+        return Y / np.std(Y[:, 0]) * 1e-4
+    Y = np.array(init, dtype=np.float64)
+    if Y.shape != (n, 2) or not np.isfinite(Y).all():
+        raise ValueError(f"tsne: init must be a finite [{n}, 2] array, got shape {Y.shape}")
+    return Y
+
+
+def tsne_learning_rate(n, early_exaggeration=12.0):
+    """sklearn's ``learning_rate='auto'``."""
+    return float(max(n / early_exaggeration / 4, 50))
+
+
+class _TsneDevice:
+    """The device side of one embedding: X's affinities, then chained descent calls on resident buffers."""
+
+    def __init__(self, X, perplexity, device=None, timed=False):
+        import torch
+
+        from . import _lib
+        if not torch.cuda.is_available():
+            raise RuntimeError("expecto_amd.cluster_and_viz needs a GPU (HIP); there is no CPU path")
+        self.torch, self.lib, self._lib = torch, _lib.load(), _lib
+        self.dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self.n, self.timed = X.shape[0], timed
+        self.affinities_ms = self.descent_ms = 0.0
+        n, d = X.shape
+        self.nbytes = int(self.lib.expecto_tsne_workspace(n))
+        with torch.cuda.device(self.dev):
+            f64 = dict(dtype=torch.float64, device=self.dev)
+            Xd = torch.from_numpy(X).to(self.dev)
+            self.P, self.beta = torch.empty((n, n), **f64), torch.empty(n, **f64)
+            self.steps = torch.empty(n, dtype=torch.int32, device=self.dev)
+            self.ws = torch.empty((self.nbytes + 7) // 8, **f64)
+            self.Y, self.update, self.gains = (torch.empty((n, 2), **f64) for _ in range(3))
+            self.stats = torch.zeros(3, **f64)
+            self.affinities_ms = self._call("expecto_tsne_affinities", Xd.data_ptr(), n, d, d, perplexity,
+                                            self.P.data_ptr(), self.beta.data_ptr(), self.steps.data_ptr(),
+                                            self.ws.data_ptr(), self.nbytes)
+
+    def _call(self, name, *args):
+        torch = self.torch
+        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)] if self.timed else None
+        if ev:
+            ev[0].record()
+        st = getattr(self.lib, name)(*args, self._lib.stream_ptr())
+        if st != 0:
+            raise RuntimeError(f"{name} failed (status {st}): {self.lib.expecto_last_error().decode()}")
+        if ev:
+            ev[1].record()
+            ev[1].synchronize()
+            return ev[0].elapsed_time(ev[1])
+        return 0.0
+
+    def start(self, Y0):
+        with self.torch.cuda.device(self.dev):
+            self.Y.copy_(self.torch.from_numpy(np.ascontiguousarray(Y0)))
+
+    def reset(self):
+        self.update.zero_()
+        self.gains.fill_(1.0)
+
+    def descend(self, exaggeration, momentum, learning_rate, n_iter):
+        """n_iter iterations; returns the call's (error, grad_norm, Z)."""
+        with self.torch.cuda.device(self.dev):
+            self.descent_ms += self._call("expecto_tsne_descend", self.P.data_ptr(), self.n, float(exaggeration),
+                                          self.Y.data_ptr(), self.update.data_ptr(), self.gains.data_ptr(),
+                                          float(momentum), float(learning_rate), int(n_iter), 1,
+                                          self.stats.data_ptr(), self.ws.data_ptr(), self.nbytes)
+            return self.stats.cpu().numpy()
+
+
+def tsne_affinities(X, perplexity=30.0, device=None):
+    """``expecto_tsne_affinities`` of X on the device: (P float64 [n, n], beta float64 [n], steps int32 [n])
+    as host arrays -- sklearn's joint probabilities in full-matrix form."""
+    X, perplexity = _tsne_checked(X, perplexity)
+    t = _TsneDevice(X, perplexity, device=device)
+    return t.P.cpu().numpy(), t.beta.cpu().numpy(), t.steps.cpu().numpy()
+
+
+def tsne(X, perplexity=30.0, early_exaggeration=12.0, learning_rate='auto', max_iter=1000, init='pca', seed=0,
+         exploration_iter=250, n_iter_check=50, n_iter_without_progress=300, min_grad_norm=1e-7, device=None,
+         timings=None) -> TSNEResult:
+    """``TSNE(n_components=2, method='exact', ...).fit_transform(X)`` on the device: the affinities in one
+    call, then sklearn's two stages (momentum 0.5 under ``early_exaggeration`` for ``exploration_iter``
+    iterations, then momentum 0.8) in chunks that end at its check points, every ``n_iter_check`` iterations,
+    where the host applies sklearn's two stopping tests to the chunk's statistics.  ``timings``: a dict
+    that receives the event-timed device ms of the affinity call and of all descent calls
+    (``affinities_ms``, ``descent_ms``).  ``ValueError`` for unsupported input, before the device is touched."""
+    X, perplexity = _tsne_checked(X, perplexity)
+    n = X.shape[0]
+    max_iter, exploration_iter, n_iter_check = int(max_iter), int(exploration_iter), int(n_iter_check)
+    if max_iter < 1 or exploration_iter < 0 or n_iter_check < 1:
+        raise ValueError("tsne: max_iter and n_iter_check must be at least 1, exploration_iter at least 0")
+    early_exaggeration = float(early_exaggeration)
+    if not (np.isfinite(early_exaggeration) and early_exaggeration >= 1.0):
+        raise ValueError("tsne: early_exaggeration must be a finite number of at least 1")
+    if isinstance(learning_rate, str):
+        if learning_rate != 'auto':
+            raise ValueError("tsne: learning_rate must be 'auto' or a positive number")
+        learning_rate = tsne_learning_rate(n, early_exaggeration)
+    learning_rate = float(learning_rate)
+    if not (np.isfinite(learning_rate) and learning_rate > 0.0):
+        raise ValueError("tsne: learning_rate must be 'auto' or a positive number")
+    Y0 = tsne_init(X, init, seed)
+
+    t = _TsneDevice(X, perplexity, device=device, timed=timings is not None)
+    t.start(Y0)
+    done, kl = 0, float('nan')
+    for end, momentum, exaggeration, window in ((min(exploration_iter, max_iter), 0.5, early_exaggeration, exploration_iter),
+                                                (max_iter, 0.8, 1.0, int(n_iter_without_progress))):
+        t.reset()       # sklearn calls _gradient_descent afresh for each stage
+        best, best_iter = np.finfo(np.float64).max, done
+        while done < end:
+            nxt = min(end, (done // n_iter_check + 1) * n_iter_check)
+            kl, grad_norm, _ = (float(v) for v in t.descend(exaggeration, momentum, learning_rate, nxt - done))
+            done = nxt
+            if done % n_iter_check == 0:
+                if kl < best:
+                    best, best_iter = kl, done - 1
+                elif done - 1 - best_iter > window:
+                    break
+                if grad_norm <= min_grad_norm:
+                    break
+    if timings is not None:
+        timings["affinities_ms"], timings["descent_ms"] = t.affinities_ms, t.descent_ms
+    return TSNEResult(t.Y.cpu().numpy(), kl, done, t.beta.cpu().numpy())
+
+
 # ---- CLI -------------------------------------------------------------------------------------
 
 def build_parser():
@@ -217,7 +393,42 @@ def build_parser():
     parser.add_argument('--seed', type=int, default=0, help='seed of the host random stream')
     parser.add_argument('--elbow', type=int, nargs=3, metavar=('K_MIN', 'K_MAX', 'STEP'), default=None,
                         help='also fit every k of range(K_MIN, K_MAX, STEP) and write elbow.tsv')
+    parser.add_argument('--tsne', action='store_true', default=False,
+                        help='also embed the marks in two dimensions (exact t-SNE): tsne_embedding.tsv, tsne.json, tsne.png')
+    parser.add_argument('--tsne_perplexity', type=float, default=30.0)
+    parser.add_argument('--tsne_iter', type=int, default=1000, help='iterations of the t-SNE descent at most')
+    parser.add_argument('--tsne_init', choices=('pca', 'random'), default='pca')
     return parser
+
+
+def write_tsne(args, X, input_features_df, labels, k):
+    """The files of ``--tsne`` (cluster_and_viz.py:60-67; the picture is saved, not shown)."""
+    import json
+
+    rate = tsne_learning_rate(X.shape[0])
+    res = tsne(X, perplexity=args.tsne_perplexity, learning_rate=rate, max_iter=args.tsne_iter, init=args.tsne_init,
+               seed=args.seed)
+    with open(f'{args.out_dir}/tsne_embedding.tsv', 'w') as f:
+        f.write('\ttsne_0\ttsne_1\tcluster\n')
+        f.writelines(f'{ix}\t{float(y[0])!r}\t{float(y[1])!r}\t{int(c)}\n'
+                     for ix, y, c in zip(input_features_df.index, res.embedding, labels))
+    with open(f'{args.out_dir}/tsne.json', 'w') as f:
+        json.dump({'kl_divergence': res.kl_divergence, 'n_iter': res.n_iter, 'perplexity': args.tsne_perplexity,
+                   'learning_rate': rate, 'init': args.tsne_init, 'seed': args.seed}, f, indent=1)
+        f.write('\n')
+    try:
+        import matplotlib
+    except ImportError:
+        return res
+    matplotlib.use('Agg')
+    import matplotlib.pyplot as plt
+    fig = plt.figure()
+    for i in range(k):
+        X_plot = res.embedding[labels == i]
+        plt.scatter(X_plot[:, 0], X_plot[:, 1], label=f'cluster {i}')
+    fig.savefig(f'{args.out_dir}/tsne.png')
+    plt.close(fig)
+    return res
 
 
 def run(args):
@@ -257,6 +468,8 @@ def run(args):
     input_features_df = beluga_features_df[keep_mask].copy()
     input_features_df['cluster'] = labels
     input_features_df.to_csv(f'{args.out_dir}/all_feature_clusters.tsv', sep='\t')
+    if args.tsne:
+        write_tsne(args, X, input_features_df, labels, k)
 
     cluster_dir = f'{args.out_dir}/clusters'
     os.makedirs(cluster_dir, exist_ok=True)

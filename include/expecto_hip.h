@@ -49,6 +49,9 @@
  *   expecto_kmeans_plusplus        the k-means++ seeding and
  *   expecto_kmeans_lloyd           the Lloyd iteration of KMeans(n_clusters=k).fit(X), batched over k and
  *                                  restarts (cluster_and_viz.py:45-58, the elbow sweep among them)
+ *   expecto_tsne_affinities        the perplexity search and joint probabilities and
+ *   expecto_tsne_descend           the gradient descent of TSNE(n_components=2, method='exact').fit_transform(X)
+ *                                  (cluster_and_viz.py:60-66)
  *   expecto_cluster_enrich         the counting of cluster_contribs_hypergeom, batched over the data, the
  *                                  shuffled controls and the SED quartiles (cluster_analysis_with_fimo.py:126-162)
  *   expecto_hypergeom_sf           its scipy.stats.hypergeom.sf (cluster_analysis_with_fimo.py:163)
@@ -567,6 +570,65 @@ int expecto_kmeans_lloyd(const double* X, long long n, long long d, long long ld
                          const long long* prob_host, const long long* prob, const double* tol, const double* init,
                          int* labels, double* centres, double* inertia, int* n_iter, void* workspace,
                          size_t workspace_bytes, void* stream);
+
+/* Exact t-SNE of the marks' SVD coordinates into two dimensions (cluster_and_viz.py:60-66:
+ * TSNE(n_components=2, random_state=0).fit_transform(X)), as sklearn's method='exact' computes it:
+ * the affinities once, then the descent in calls of n_iter iterations that the host chains.
+ * Supported: 2 <= n <= 4096, 1 <= d <= 128, 0 < perplexity < n; everything else is EXPECTO_EINVAL
+ * with a message, as are ld < d, a null pointer, a non-finite exaggeration, momentum or
+ * learning_rate, n_iter outside [0, 2^31), and a workspace smaller than expecto_tsne_workspace(n)
+ * bytes (a pure host function that covers either call; 0 for a refused n) or not 8-byte aligned.
+ * All pointers but the workspace's size are DEVICE memory.
+ *
+ * The arithmetic is fixed.  All of it is float64, products and sums rounded separately (no FMA), no
+ * atomics; / and sqrt are IEEE.  Two identical calls give identical bits, whatever the launch
+ * geometry.  Only exp and log (the bisection's p and H, the error) are the device library's and
+ * differ from another library's by ulps.
+ *   wave-order sum of a[0..m):  (1) lane l of 64 computes s_l = +0.0, then s_l = s_l + a[j] for
+ *     j = l, l + 64, ... ascending;  (2) for w = 32, 16, 8, 4, 2, 1 in that order, s_l = s_l + s_{l+w}
+ *     for every l < w;  (3) the sum is s_0.
+ *   Every sum below is in wave order.  A sum "over j" belongs to row i, and its term for j = i is +0.0.
+ *
+ * expecto_tsne_affinities: sklearn's _joint_probabilities with _binary_search_perplexity, on float64
+ * distances (sklearn rounds them to float32 first) and with the full matrix for its condensed one.
+ * X is float64 [n, d] with row stride ld >= d; the padding is never read.
+ *   D_ij:  s = +0.0; for t = 0..d-1 in order u = x_it - x_jt, s = s + u*u.
+ *   Row i, at most 100 steps from beta = 1, beta_min = -inf, beta_max = +inf:
+ *     p_j = exp(-D_ij * beta) (j != i);  S = sum_j p_j, and S = 1e-8 if S == 0;  p_j = p_j / S;
+ *     H = log(S) + beta * sum_j (D_ij * p_j);  diff = H - log(perplexity) (the host's log);
+ *     stop if |diff| <= 1e-5;  else if diff > 0: beta_min = beta, and beta = 2 * beta while beta_max
+ *     is +inf, else beta = (beta + beta_max) / 2;  else beta_max = beta, and beta = beta / 2 while
+ *     beta_min is -inf, else beta = (beta + beta_min) / 2.
+ *     c_ij = the p_j of the last step taken, c_ii = 0.  beta[i] = the beta of that step, steps[i] =
+ *     the steps taken (1..100).
+ *   r_i = sum_j (c_ij + c_ji);  T = sum_i r_i;
+ *   P_ij = max((c_ij + c_ji) / max(T, eps), eps) for i != j, P_ii = 0, eps = DBL_EPSILON.  P is
+ *   symmetric to the bit.
+ * Outputs: P float64 [n, n], beta float64 [n], steps int32 [n].
+ *
+ * expecto_tsne_descend: n_iter iterations of sklearn's _gradient_descent over _kl_divergence with one
+ * degree of freedom, enqueued back to back: two launches per iteration and one to close the call, no
+ * host synchronisation.  Y, update and gains are float64 [n, 2], read and written, so calls chain:
+ * one call of a + b iterations gives the bits of a call of a and then a call of b.  Y is never
+ * updated while it is read: an iteration reads one copy and writes the other (the workspace holds
+ * the second).  n_iter = 0 succeeds and writes nothing.  One iteration:
+ *   pass A   a = y_i0 - y_j0, b = y_i1 - y_j1, num_ij = 1 / (1 + (a*a + b*b));  z_i = sum_j num_ij;
+ *            Z = sum_i z_i.
+ *   pass B   q = max(num_ij / Z, eps);  t = (exaggeration * P_ij - q) * num_ij;
+ *            g_i0 = 4 * sum_j (t * a),  g_i1 = 4 * sum_j (t * b).
+ *   update   per element e of [n, 2]:  gain_e = gain_e + 0.2 if update_e * g_e < 0, else gain_e * 0.8;
+ *            gain_e = max(gain_e, 0.01);  g_e = g_e * gain_e;
+ *            update_e = momentum * update_e - learning_rate * g_e;  y_e = y_e + update_e.
+ * stats (float64 [3]) describes the call's last iteration:  stats[1] = sqrt(sum over the 2n entries,
+ * row-major, of g_e * g_e) with g after its gain (sklearn's norm is taken there);  stats[2] = Z;  and
+ * only if want_error != 0, stats[0] = sum_i (sum_j (P'_ij * log(max(P'_ij, eps) / q_ij))) with
+ * P' = exaggeration * P: sklearn's KL divergence, its 2 * sum over i < j taken over the ordered pairs. */
+size_t expecto_tsne_workspace(long long n);
+int expecto_tsne_affinities(const double* X, long long n, long long d, long long ld, double perplexity, double* P,
+                            double* beta, int* steps, void* workspace, size_t workspace_bytes, void* stream);
+int expecto_tsne_descend(const double* P, long long n, double exaggeration, double* Y, double* update, double* gains,
+                         double momentum, double learning_rate, long long n_iter, int want_error, double* stats,
+                         void* workspace, size_t workspace_bytes, void* stream);
 
 /* Motif-match enrichment of the top clusters (cluster_analysis_with_fimo.py:126-162: the counting of
  * cluster_contribs_hypergeom), as P problems over one contribution matrix per call.
