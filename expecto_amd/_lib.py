@@ -128,6 +128,11 @@ SIGNATURES = {
     "expecto_pwm_scan": (ctypes.c_int, [c_vp, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, c_vp, c_vp, c_vp,
                                         c_vp, ctypes.c_longlong, c_vp, c_vp, ctypes.c_longlong, c_vp, c_vp, c_vp, c_vp,
                                         c_vp]),
+    "expecto_pwm_compare": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_longlong, ctypes.c_int, c_vp, c_vp, c_vp, c_vp,
+                                           c_vp, c_vp, c_vp]),
+    "expecto_average_linkage": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp, c_vp, c_vp]),
+    "expecto_linkage_threshold_cut": (ctypes.c_int, [c_vp, ctypes.c_int, c_vp, c_vp, ctypes.c_double, ctypes.c_double,
+                                                     c_vp, c_vp, c_vp]),
     "expecto_rank2_f32": (ctypes.c_int, [c_vp, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, c_vp, c_vp]),
     "expecto_rank2_f64": (ctypes.c_int, [c_vp, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, c_vp, c_vp]),
     "expecto_model_metrics": (ctypes.c_int, [c_vp, ctypes.c_longlong, c_vp, ctypes.c_longlong, c_vp, c_vp,

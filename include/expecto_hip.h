@@ -58,6 +58,9 @@
  *   expecto_pwm_pvalues            the score-to-p-value tables of `fimo` (query_fimo_for_predictions.py:45) and
  *   expecto_pwm_scan               its matches, reduced to the best one that overlaps the variant per motif
  *                                  and sequence (query_fimo_for_predictions.py:53-57)
+ *   expecto_pwm_compare            the pairwise motif comparison (cor, Ncor over all offsets, both strands),
+ *   expecto_average_linkage        the tree and
+ *   expecto_linkage_threshold_cut  the clusters that follow cluster_by_pwm.py's cluster_motifs.jaspar
  *   expecto_rank2_f32 / _f64       scipy's rankdata inside spearmanr (train.py:150,163; train_bootstrap.py:110,124)
  *   expecto_model_metrics          pearsonr, spearmanr and r2_score of a model's predictions
  *                                  (train_susztak.py:153-154; train.py:163,171-172; train_bootstrap.py:124,132-133;
@@ -725,6 +728,56 @@ int expecto_pwm_scan(const unsigned char* codes, long long S, long long L, long 
                      const short* pssm, const int* col_ptr_host, const int* col_ptr, long long M, const double* tables,
                      const long long* pv_ptr, long long tables_len, int* score, int* start, unsigned char* strand,
                      double* pvalue, void* stream);
+
+/* Motif similarity clustering (cluster_by_pwm.py writes cluster_motifs.jaspar for RSAT matrix-clustering,
+ * which is not part of this project): every pair of motifs compared at every offset on both strands, an
+ * average-linkage tree of the distances and its cut by two thresholds.  The arithmetic follows RSAT's
+ * published definitions of cor, Ncor and average linkage and is fixed below; agreement with RSAT itself
+ * has not been measured.
+ *
+ * expecto_pwm_compare.  freq float64 [col_ptr[M], 4] (DEVICE): the frequencies of all motifs, a row per
+ * motif column, the four entries in alphabet order A C G T; every row sums to 1 up to rounding, so the
+ * mean over any set of whole columns is 0.25 and the centred value is a = f - 0.25.  col_ptr int32
+ * [M + 1], passed twice with the same contents, in HOST memory (checked: starts at 0, widths in [1, 64])
+ * and in DEVICE memory (a motif that does not fit the checked sizes is passed over, and so are its pairs).
+ * For the pair (A, B) = motifs (i < j) of widths wA, wB:
+ *   strands    D compares A with B, R with B_rc[c][b] = B[wB-1-c][3-b];
+ *   offsets    o is the column of A under column 0 of B (or B_rc); need = min(min_w, wA, wB); o runs from
+ *              -(wB - need) to wA - need; the overlap is A's columns [max(0, o), min(wA, o + wB)), w wide;
+ *   sums       num = S a*b, ssa = S a*a, ssb = S b*b over the overlap, A's columns ascending and A C G T
+ *              within a column, each sum one chain s = +0.0, s = s + x*y in float64, the product rounded
+ *              before the add (no FMA);
+ *   scores     cor = num / sqrt(ssa * ssb), or 0 when ssa * ssb == 0 (IEEE / and sqrt);
+ *              Ncor = cor * (double)w / (double)(wA + wB - w), evaluated left to right;
+ *   best       the largest Ncor; equal Ncor to strand D before R, then to the smaller o.
+ * Outputs (DEVICE), M(M-1)/2 entries each, pair (i < j) at scipy's condensed index
+ * M i - i(i+1)/2 + (j - i - 1):  cor, ncor float64, the best alignment's;  dist float64 = 1 - Ncor, or 0 if
+ * that is negative;  offset int32 = o;  strand int32, 0 for D and 1 for R;  width int32 = w.
+ * Plain vector stores, no atomics: a pair's bits depend on nothing but the two motifs and min_w.  A
+ * workgroup takes a 16 x 16 tile of pairs of the upper triangle, one lane per pair.  Refused
+ * (EXPECTO_EINVAL, nothing launched or written): M outside [0, 4096], min_w < 1, a width outside [1, 64],
+ * col_ptr[0] != 0, a decreasing col_ptr, a null pointer with M >= 2.  M < 2 succeeds without a launch.
+ *
+ * expecto_average_linkage (HOST memory throughout): scipy's linkage(method='average') of n(n-1)/2
+ * condensed distances, which are overwritten: the NN-chain algorithm with strict < and the previous chain
+ * element preferred, the update d(k, x u y) = (n_x d_kx + n_y d_ky) / (n_x + n_y) evaluated left to right,
+ * a stable sort of the merges by height and a union-find relabelling.  Row i of children int32 [n-1, 2],
+ * heights float64 [n-1] and sizes int32 [n-1] is the i-th merge by height; it forms cluster n + i out of
+ * children[i] (smaller id first).  Refused: n < 2, a NaN distance, a cluster whose every distance is +inf.
+ *
+ * expecto_linkage_threshold_cut (HOST memory throughout): children as above; cor, ncor float64 [n(n-1)/2].
+ * For merge i of the clusters X = children[i][0] and Y = children[i][1], mean_cor[i] is s = +0.0, then
+ * s = s + cor[x, y] over X's leaves ascending (outer) and Y's leaves ascending (inner), then
+ * s / (double)(|X| |Y|); mean_ncor[i] likewise.  Merge i is accepted when both children are leaves or
+ * accepted merges and mean_cor[i] >= min_cor and mean_ncor[i] >= min_ncor.  The clusters are the maximal
+ * accepted nodes (a leaf under no accepted merge is its own); labels int32 [n] are 1-based, numbered by
+ * ascending smallest member index.  Refused: n < 2, children that do not form a tree (a child outside
+ * [0, n + i) or used twice), a null pointer. */
+int expecto_pwm_compare(const double* freq, const int* col_ptr_host, const int* col_ptr, long long M, int min_w,
+                        double* cor, double* ncor, double* dist, int* offset, int* strand, int* width, void* stream);
+int expecto_average_linkage(double* condensed, int n, int* children, double* heights, int* sizes);
+int expecto_linkage_threshold_cut(const int* children, int n, const double* cor, const double* ncor, double min_cor,
+                                  double min_ncor, int* labels, double* mean_cor, double* mean_ncor);
 
 /* Scores of trained models and statistics of a bootstrap batch (train_susztak.py:146-181,
  * plot_bootstrapped_coefficients.py:52-76).  All pointers are DEVICE memory, strides are in elements, and a
