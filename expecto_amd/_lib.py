@@ -116,6 +116,12 @@ SIGNATURES = {
     "expecto_tsne_descend": (ctypes.c_int, [c_vp, ctypes.c_longlong, ctypes.c_double, c_vp, c_vp, c_vp,
                                             ctypes.c_double, ctypes.c_double, ctypes.c_longlong, ctypes.c_int, c_vp,
                                             c_vp, ctypes.c_size_t, c_vp]),
+    "expecto_knn_jaccard": (ctypes.c_int, [c_vp, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong,
+                                           ctypes.c_longlong, c_vp, c_vp, c_vp]),
+    "expecto_louvain_workspace": (ctypes.c_size_t, [ctypes.c_longlong] * 3),
+    "expecto_louvain": (ctypes.c_int, [c_vp, c_vp, c_vp, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong,
+                                       c_vp, c_vp, ctypes.c_longlong, ctypes.c_longlong, c_vp, c_vp, c_vp, c_vp,
+                                       ctypes.c_size_t, c_vp]),
     "expecto_cluster_enrich_workspace": (ctypes.c_size_t, [ctypes.c_longlong] * 2),
     "expecto_cluster_enrich": (ctypes.c_int, [c_vp, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_longlong, c_vp,
                                               ctypes.c_longlong, c_vp, c_vp, c_vp, ctypes.c_longlong, c_vp, c_vp,

@@ -52,7 +52,10 @@
  *   expecto_tsne_affinities        the perplexity search and joint probabilities and
  *   expecto_tsne_descend           the gradient descent of TSNE(n_components=2, method='exact').fit_transform(X)
  *                                  (cluster_and_viz.py:60-66)
- *   expecto_cluster_enrich         the counting of cluster_contribs_hypergeom, batched over the data, the
+ *   expecto_knn_jaccard            the k-nearest-neighbour graph with Jaccard weights and
+ *   expecto_louvain                the Louvain communities of it, batched over resolutions and restarts
+ *                                  (cluster_and_viz_louvain.py:48-53)
+ *   expecto_cluster_enrich        the counting of cluster_contribs_hypergeom, batched over the data, the
  *                                  shuffled controls and the SED quartiles (cluster_analysis_with_fimo.py:126-162)
  *   expecto_hypergeom_sf           its scipy.stats.hypergeom.sf (cluster_analysis_with_fimo.py:163)
  *   expecto_pwm_pvalues            the score-to-p-value tables of `fimo` (query_fimo_for_predictions.py:45) and
@@ -632,6 +635,81 @@ int expecto_tsne_affinities(const double* X, long long n, long long d, long long
 int expecto_tsne_descend(const double* P, long long n, double exaggeration, double* Y, double* update, double* gains,
                          double momentum, double learning_rate, long long n_iter, int want_error, double* stats,
                          void* workspace, size_t workspace_bytes, void* stream);
+
+/* Louvain clustering of the marks' SVD coordinates (cluster_and_viz_louvain.py: Orange's Louvain(5) on
+ * the first 20 coordinates): the k-nearest-neighbour graph with Jaccard weights, then communities of
+ * maximal modularity (Blondel et al. 2008, with the resolution of Reichardt and Bornholdt).  Orange and
+ * python-louvain were not available: the algorithm is defined here, from the published definitions, and
+ * anchored to scikit-learn's NearestNeighbors and networkx's modularity by the tests; agreement with
+ * Orange is unmeasured.  All pointers but a workspace's size are DEVICE memory.
+ *
+ * The arithmetic is fixed.  All of it is float64, products and sums rounded separately (no FMA), no
+ * floating-point atomics; / is IEEE.  "Chain" is the sequential sum of the k-means contract: s = +0.0,
+ * then s = s + a[i] in the order given.  Two identical calls give identical bits, and a problem's bits
+ * depend on nothing but its own inputs.
+ *
+ * expecto_knn_jaccard.  X float64 [n, d], row stride ld >= d, the padding never read.  Supported:
+ * 1 <= n <= 4096, 1 <= d <= 128, 1 <= k <= min(n, 64); everything else, and a null pointer, is
+ * EXPECTO_EINVAL with a message and nothing launched.
+ *   d2(i, j):  s = +0.0; for c = 0..d-1 in order t = x_ic - x_jc, s = s + t*t (plain multiply and add).
+ *   N(i) = the k points j of smallest (d2(i, j), j), i itself a candidate: what
+ *     NearestNeighbors(n_neighbors=k).fit(X).kneighbors(X) returns when no distances tie.
+ *   nbr int32 [n, k]: N(i) in ascending (d2, j).
+ *   w float64 [n, k]: for j = nbr[i, t], c = |N(i) & N(j)| as sets, w[i, t] = (double)c / (double)(2k - c);
+ *     0 where j == i.
+ *
+ * expecto_louvain: P problems over one undirected weighted graph in CSR form: indptr int32 [n + 1],
+ * indices int32 [nnz], weights float64 [nnz]; every edge {u, v} is stored in both rows with the same
+ * weight, and the input holds no self-loop.  Problem p has the resolution gamma[p] (float64 [P]) and the
+ * visiting order perm[p] (int32 [P, n], each row a permutation of 0..n-1).  One wave runs one problem.
+ * Supported: 1 <= n <= 4096, 0 <= nnz <= 1048576, 0 <= P <= 65535, 1 <= max_passes <= 1000,
+ * 1 <= max_levels <= 64; everything else, a null pointer, a workspace smaller than
+ * expecto_louvain_workspace(n, nnz, P) bytes (a pure host function; 0 for a refused shape) or not 8-byte
+ * aligned is EXPECTO_EINVAL.  P = 0 writes nothing and succeeds.  The graph and the orders are never seen
+ * by the host: a problem whose indptr does not rise from 0 to nnz, or with an index or an order entry
+ * outside [0, n), writes only modularity 0, counters 0 and the flag EXPECTO_LOUVAIN_BAD_GRAPH.
+ *
+ * A level works on a graph whose rows may hold a self-loop entry (v, v), of weight s: the weight inside
+ * v, each edge once.
+ *   degree      k_v = the chain over row v in row order, the self-loop entry as 2*s;  2m = the chain of
+ *               k_v over v ascending.  If 2m == 0 at level 0 every node is its own community:
+ *               modularity 0, n_levels 0, n_passes 0, flags 0.
+ *   start       every node in its own slot: comm[v] = v, D[v] = k_v.
+ *   pass        visit v in perm's order at level 0, in ascending v above it.  old = comm[v];
+ *               D[old] = D[old] - k_v.  For every slot c = comm[x] of an entry x != v of row v,
+ *               k_vc = the chain of the row's weights towards c in row order; k_v,old = +0.0 if the row
+ *               has no such entry.  gain(c) = k_vc - ((gamma * D[c]) * k_v) / 2m.  v goes to the slot of
+ *               largest gain, old if it ties for it, else the lowest such slot: to.
+ *               D[to] = D[to] + k_v (also when to == old).
+ *   Q           lin_v = the chain, in row order, of row v's weights towards x >= v with comm[x] == comm[v];
+ *               L_c = the chain of lin_v over the slot's nodes v ascending;
+ *               Q = the chain over all slots c ascending, empty ones too, of
+ *               L_c / (2m * 0.5) - gamma * ((D[c] / 2m) * (D[c] / 2m)), with D as the passes left it.
+ *               This is networkx.community.modularity(G, parts, weight='weight', resolution=gamma).
+ *   level       Q is taken once before the first pass of level 0 and after every pass.  Passes end after
+ *               a pass that moved no node or raised Q by less than 1e-7, and after max_passes passes
+ *               (flag EXPECTO_LOUVAIN_PASS_BOUND unless that pass also met a stop).  A level whose
+ *               passes moved no node ends the run.
+ *   aggregate   slots are renumbered in ascending order of their smallest node; labels follow.  New
+ *               node C's entry towards C' != C is the chain of w(u, x) over C's nodes u ascending and
+ *               their rows in order, for comm[x] == C'; its self-loop is the same chain over
+ *               comm[x] == C and x >= u, present if that chain has a term.  Rows are in ascending
+ *               neighbour id, the self-loop in its place.  Degrees and 2m are taken anew.
+ *   run         After aggregating, the run ends if Q rose by less than 1e-7 over the level; after
+ *               max_levels levels it ends with the flag EXPECTO_LOUVAIN_LEVEL_BOUND.
+ * Outputs: labels int32 [P, n], communities numbered in ascending order of their smallest node;
+ * modularity float64 [P], the last Q taken; counters int32 [P, 4]: n_communities, n_levels (the levels
+ * aggregated), n_passes (all levels') and flags. */
+#define EXPECTO_LOUVAIN_PASS_BOUND 1
+#define EXPECTO_LOUVAIN_LEVEL_BOUND 2
+#define EXPECTO_LOUVAIN_BAD_GRAPH 4
+int expecto_knn_jaccard(const double* X, long long n, long long d, long long ld, long long k, int* nbr, double* w,
+                        void* stream);
+size_t expecto_louvain_workspace(long long n, long long nnz, long long P);
+int expecto_louvain(const int* indptr, const int* indices, const double* weights, long long n, long long nnz,
+                    long long P, const double* gamma, const int* perm, long long max_passes, long long max_levels,
+                    int* labels, double* modularity, int* counters, void* workspace, size_t workspace_bytes,
+                    void* stream);
 
 /* Motif-match enrichment of the top clusters (cluster_analysis_with_fimo.py:126-162: the counting of
  * cluster_contribs_hypergeom), as P problems over one contribution matrix per call.
