@@ -145,6 +145,12 @@ SIGNATURES = {
                                              ctypes.c_int, ctypes.c_int, c_vp, c_vp]),
     "expecto_bootstrap_coef_stats": (ctypes.c_int, [c_vp, ctypes.c_longlong, ctypes.c_int, ctypes.c_int, c_vp, c_vp,
                                                     c_vp, c_vp, c_vp, c_vp]),
+    "expecto_ism_variants": (ctypes.c_int, [c_vp, ctypes.c_longlong, ctypes.c_longlong, ctypes.c_int, c_vp, c_vp, c_vp,
+                                            c_vp, c_vp]),
+    "expecto_ism_score": (ctypes.c_int, [c_vp, c_vp, ctypes.c_longlong, c_vp, ctypes.c_int, c_vp, ctypes.c_int,
+                                         ctypes.c_int, ctypes.c_int, c_vp, ctypes.c_int, c_vp, ctypes.c_int, c_vp, c_vp,
+                                         ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "expecto_ism_summary": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp]),
     "expecto_last_error": (ctypes.c_char_p, []),
     "expecto_version": (ctypes.c_char_p, []),
 }

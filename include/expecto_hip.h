@@ -70,6 +70,8 @@
  *                                   geuvadis_predict_consensus.py:254-256 and its _for_top_eqtls copy)
  *   expecto_bootstrap_coef_stats   np.std(ddof=1) / np.mean over the bootstrap models, the z-score and the
  *                                  coefficient of variation (plot_bootstrapped_coefficients.py:56,64,75)
+ *   expecto_ism_variants / _score  no reference script: saturation mutagenesis, i.e. every SNV of a region
+ *   expecto_ism_summary            through chromatin.py, make_closest_genes_file.py and predict.py per model
  *   expecto_beluga_destroy         (model teardown)
  */
 #ifndef EXPECTO_HIP_H
@@ -896,6 +898,50 @@ int expecto_model_metrics(const float* pred, long long pred_stride, const double
                           const int* rank_pred, const int* rank_y, int n, int P, double* out, void* stream);
 int expecto_bootstrap_coef_stats(const double* W, long long ld, int B, int F, const double* w_main, double* mean,
                                  double* se, double* z, double* cv, void* stream);
+
+/* In-silico saturation mutagenesis: every SNV of a region, enumerated and scored on the device (the
+ * reference has no script for it; it would be a VCF of 3 L SNVs through chromatin.py,
+ * make_closest_genes_file.py and predict.py once per tissue model).  All pointers are DEVICE memory unless
+ * noted; a refused call (EXPECTO_EINVAL) launches and writes nothing.
+ *
+ * expecto_ism_variants: the SNVs of the L genome offsets start .. start + L - 1 (0 <= start,
+ * start + L <= genome_len; code alphabet of expecto_variant_windows: 0=A 1=G 2=C 3=T 4=zero column).  3 L
+ * slots, slot 3*p + j of position p: var_off (int64) = start + p; ref_code = genome[start + p]; alt_code = the
+ * j-th of the base codes 0..3, in code order, that is not ref_code; valid (uint8) = 1.  A position whose code
+ * is not a base gets valid = 0 and alt_code = ref_code in its three slots: its windows are no-ops and nothing
+ * downstream needs compaction.  Slots are fixed (no atomics, no scan): the output does not depend on the grid.
+ *
+ * expecto_ism_score: expression predictions of both alleles of every slot for n_models gblinear models at
+ * once, without the [n, 10*nfeat] float64 feature matrices.  y_ref, y_alt: float32 chromatin rows of both
+ * strands as expecto_beluga_forward_segment_pairs writes them for rows="shift": row s*strand_stride + j*n + v
+ * for strand s, shift j (n_shift of them, the order of `shifts`) and slot v (n of them, n % 3 == 0, three per
+ * position); strand_stride >= n_shift*n.  dist[n] (pos - TSS, int64), shifts, exp_lut, lut_len: as
+ * expecto_variant_reduce_lut; strand_plus: HOST scalar, the gene's strand (one gene per call).  keep[nk]: the
+ * kept mark columns, ascending, each in 0..nfeat-1.  w: float32 [10*nk, n_models], model m's weight of feature
+ * column c = k*nk + f at w[c*n_models + m] (the models of a wave read one contiguous run per column);
+ * init[n_models]: float32(bias + base_score) of each model.  valid[n]: as expecto_ism_variants gives it.
+ * Outputs: alt_pred float32 [n_models, n]; ref_pred float32 [n_models, n/3], one per position, from the ref
+ * rows and the distance of the position's first slot (the three slots of a position hold the same ref window);
+ * sed float64 [n_models, n] = (double)alt_pred - (double)ref_pred[position].  An invalid slot gets NaN in
+ * alt_pred and sed; a position with three invalid slots gets NaN in ref_pred.
+ * Arithmetic: bitwise what the unfused chain gives on the same rows -- expecto_fwd_rc_average of each allele,
+ * expecto_variant_reduce_lut (float64, shifts summed in order from the first term, a distance bin
+ * fl >= lut_len through the device exp), expecto_gblinear_predict per model over the columns k*nfeat + keep[f]
+ * (float32, init first, column order, every product and sum rounded on its own, no FMA).  One workgroup per
+ * position and 256 models; no atomics: results do not depend on n_models, n or the grid.
+ * 240*n_shift + 16*nk bytes of LDS must fit 160 KiB and n_shift <= 819, else EXPECTO_EINVAL.
+ *
+ * expecto_ism_summary: potential[m] = S(|sed[m, .]|) and direction[m] = S(sed[m, .]) over the n slots in slot
+ * order (float64 [n_models] each), S the fixed order of expecto_variant_contrib; an invalid slot's term is
+ * -0.0, which changes no sum.  One wave per model. */
+int expecto_ism_variants(const uint8_t* genome, long long genome_len, long long start, int L, long long* var_off,
+                         uint8_t* ref_code, uint8_t* alt_code, uint8_t* valid, void* stream);
+int expecto_ism_score(const float* y_ref, const float* y_alt, long long strand_stride, const long long* dist,
+                      int strand_plus, const int* shifts, int n_shift, int n, int nfeat, const double* exp_lut,
+                      int lut_len, const int* keep, int nk, const float* w, const float* init, int n_models,
+                      const uint8_t* valid, float* alt_pred, float* ref_pred, double* sed, void* stream);
+int expecto_ism_summary(const double* sed, const uint8_t* valid, int n_models, int n, double* potential,
+                        double* direction, void* stream);
 
 const char* expecto_last_error(void);
 const char* expecto_version(void);
