@@ -76,6 +76,9 @@ SIGNATURES = {
                                                     c_vp, ctypes.c_longlong, c_vp, ctypes.c_longlong, c_vp, c_vp,
                                                     ctypes.c_int, ctypes.c_double, ctypes.c_double, ctypes.c_double,
                                                     ctypes.c_double, ctypes.c_float, c_vp, c_vp]),
+    "expecto_gblinear_train_round_hp": (ctypes.c_int, [c_vp, ctypes.c_longlong, ctypes.c_int, ctypes.c_int,
+                                                       ctypes.c_int, c_vp, ctypes.c_longlong, c_vp, ctypes.c_longlong,
+                                                       c_vp, c_vp, ctypes.c_int, c_vp, ctypes.c_float, c_vp, c_vp]),
     "expecto_gblinear_predict_cols": (ctypes.c_int, [c_vp, ctypes.c_longlong, ctypes.c_int, ctypes.c_int,
                                                      ctypes.c_int, c_vp, ctypes.c_float, c_vp, c_vp]),
     "expecto_gblinear_rmse": (ctypes.c_int, [c_vp, c_vp, ctypes.c_longlong, c_vp, ctypes.c_longlong, ctypes.c_int,

@@ -3,7 +3,8 @@
 // descent on weighted ridge / elastic-net least squares (GBLinear::DoBoost plus the learner's
 // round loop; the arithmetic is restated in DESIGN.md "Training gblinear models").
 //
-//  * gbl_round_kernel        one boosting round of one model per 1024-thread workgroup;
+//  * gbl_round_kernel        one boosting round of one model per 1024-thread workgroup, with one
+//                            set of hyper-parameters for the launch or one per model;
 //  * gbl_predict_cols_kernel the gblinear margin on the column-major float32 matrix;
 //  * gbl_rmse_kernel         xgboost's weighted rmse.
 //
@@ -103,6 +104,17 @@ struct TrainHyper {
   double eta, lambda, alpha, lambda_bias;
 };
 
+// Where a launch's hyper-parameters come from.  One TrainHyper kernel argument serves every model
+// of the launch (expecto_gblinear_train_round); a [n_models, 4] table of doubles gives model m its
+// own row (expecto_gblinear_train_round_hp).  The row's address depends on blockIdx.x alone and
+// nothing is stored before it is read, so the four doubles arrive by scalar loads and stay in
+// scalar registers, as the kernel argument does: no lane holds a copy.
+__device__ __forceinline__ TrainHyper hyper_of(const TrainHyper& hp, int) { return hp; }
+__device__ __forceinline__ TrainHyper hyper_of(const double* hyper, int m) {
+  const double* row = hyper + 4 * (long long)m;
+  return TrainHyper{row[0], row[1], row[2], row[3]};
+}
+
 // One coordinate: sg = sum g*x (sh = sum (h*x)*x in the first round, stored; read afterwards:
 // it does not change between rounds), dw from the same numbers on every lane, g += (h*x)*dw.
 template <bool FIRST>
@@ -154,14 +166,16 @@ __device__ __forceinline__ void cd_step(float (&g)[kTrainRows], const float (&x)
 // pass, its 24 row weights in LDS (96 KB, read only by the lane that wrote them), and the
 // columns of X come through two register buffers: column j+1 is loaded before column j is
 // reduced, so a feature's dependent chain is its reduction, not a memory round trip.
-template <bool FIRST>
+// HP: TrainHyper (by value, for every model) or const double* (a row per model), see hyper_of.
+template <bool FIRST, class HP>
 __global__ __launch_bounds__(kTrainThreads) void gbl_round_kernel(
     const float* __restrict__ X, long long ld, int n, int F, const float* __restrict__ y, long long y_stride,
-    const float* __restrict__ h, long long h_stride, float* w, double* sh, TrainHyper hp, float base_score,
+    const float* __restrict__ h, long long h_stride, float* w, double* sh, HP hyper, float base_score,
     float* __restrict__ pred) {
   __shared__ float4 hl[kTrainRows / 4 * kTrainThreads];
   __shared__ double slots[2][2 * kTrainWaves];
   const int m = blockIdx.x, t = threadIdx.x;
+  const TrainHyper hp = hyper_of(hyper, m);
   float* const wm = w + (long long)m * (F + 1);
   double* const shm = sh + (long long)m * F;
   float b = wm[F];
@@ -290,6 +304,29 @@ __global__ __launch_bounds__(kTrainThreads) void gbl_rmse_kernel(const float* __
   if (threadIdx.x == 0) out[m] = sqrt(v[0] / v[1]);
 }
 
+// The host side both entry points share: shapes, strides, the row cap, then the launch.
+static int check_train_round(const float* X, long long ld, int n, int num_feature, const float* y, long long y_stride,
+                             long long h_stride, const float* w, const double* sh) {
+  EXPECTO_REQUIRE(n <= EXPECTO_GBLINEAR_TRAIN_MAX_ROWS, "gblinear training holds at most 24576 rows per model");
+  EXPECTO_REQUIRE(ld >= n && y_stride >= 0 && h_stride >= 0, "bad stride (ld >= n)");
+  EXPECTO_REQUIRE(y && w && (num_feature == 0 || (X && sh)), "null argument");
+  return EXPECTO_OK;
+}
+
+template <class HP>
+static int launch_train_round(const float* X, long long ld, int n, int num_feature, int n_models, const float* y,
+                              long long y_stride, const float* h, long long h_stride, float* w, double* sh, int first,
+                              HP hyper, float base_score, float* pred, void* stream) {
+  const dim3 grid((unsigned)n_models), block(kTrainThreads);
+  if (first)
+    gbl_round_kernel<true, HP><<<grid, block, 0, as_stream(stream)>>>(X, ld, n, num_feature, y, y_stride, h, h_stride,
+                                                                      w, sh, hyper, base_score, pred);
+  else
+    gbl_round_kernel<false, HP><<<grid, block, 0, as_stream(stream)>>>(X, ld, n, num_feature, y, y_stride, h, h_stride,
+                                                                       w, sh, hyper, base_score, pred);
+  return check_launch("gblinear_train_round");
+}
+
 }  // namespace expecto
 
 using namespace expecto;
@@ -302,18 +339,20 @@ int expecto_gblinear_train_round(const float* X, long long ld, int n, int num_fe
                                  float base_score, float* pred, void* stream) {
   EXPECTO_REQUIRE(n >= 0 && num_feature >= 0 && n_models >= 0, "negative shape");
   if (n == 0 || n_models == 0) return EXPECTO_OK;
-  EXPECTO_REQUIRE(n <= EXPECTO_GBLINEAR_TRAIN_MAX_ROWS, "gblinear training holds at most 24576 rows per model");
-  EXPECTO_REQUIRE(ld >= n && y_stride >= 0 && h_stride >= 0, "bad stride (ld >= n)");
-  EXPECTO_REQUIRE(y && w && (num_feature == 0 || (X && sh)), "null argument");
-  const TrainHyper hp{eta, lambda, alpha, lambda_bias};
-  const dim3 grid((unsigned)n_models), block(kTrainThreads);
-  if (first)
-    gbl_round_kernel<true><<<grid, block, 0, as_stream(stream)>>>(X, ld, n, num_feature, y, y_stride, h, h_stride, w,
-                                                                  sh, hp, base_score, pred);
-  else
-    gbl_round_kernel<false><<<grid, block, 0, as_stream(stream)>>>(X, ld, n, num_feature, y, y_stride, h, h_stride, w,
-                                                                   sh, hp, base_score, pred);
-  return check_launch("gblinear_train_round");
+  if (const int st = check_train_round(X, ld, n, num_feature, y, y_stride, h_stride, w, sh)) return st;
+  return launch_train_round(X, ld, n, num_feature, n_models, y, y_stride, h, h_stride, w, sh, first,
+                            TrainHyper{eta, lambda, alpha, lambda_bias}, base_score, pred, stream);
+}
+
+int expecto_gblinear_train_round_hp(const float* X, long long ld, int n, int num_feature, int n_models, const float* y,
+                                    long long y_stride, const float* h, long long h_stride, float* w, double* sh,
+                                    int first, const double* hyper, float base_score, float* pred, void* stream) {
+  EXPECTO_REQUIRE(n >= 0 && num_feature >= 0 && n_models >= 0, "negative shape");
+  if (n == 0 || n_models == 0) return EXPECTO_OK;
+  if (const int st = check_train_round(X, ld, n, num_feature, y, y_stride, h_stride, w, sh)) return st;
+  EXPECTO_REQUIRE(hyper, "null argument");
+  return launch_train_round(X, ld, n, num_feature, n_models, y, y_stride, h, h_stride, w, sh, first, hyper, base_score,
+                            pred, stream);
 }
 
 int expecto_gblinear_predict_cols(const float* X, long long ld, int n, int num_feature, int n_models, const float* w,

@@ -26,6 +26,18 @@ on its chr8 rows, labels in float64) and writes ``<output_dir>/metrics/metrics.h
 of ``train_susztak.py:177-181`` plus ``spearmanr_trains`` / ``spearmanr_valids``, in model order)
 and ``metrics.tsv``.  Both are off by default, and then nothing changes.
 
+``--cv K`` chooses the penalties and the number of rounds per target by K-fold cross-validation
+(:func:`expecto_amd.xgblinear.cv`) before it trains: the folds are whole chromosomes of the
+training rows (``chromosome_folds``), the grid is ``--l2-grid`` x ``--l1-grid`` (each defaults to
+the single ``--l2`` / ``--l1``) from most to least regularised, every round up to ``--num_round``
+is a candidate, and ``--cv-rule`` picks the least mean held-out rmse (``min``) or the most
+regularised grid point within one standard error of it (``1se``).  ``cv.tsv`` (one row per target,
+l2, l1 and round: score, se and the held-out rmse of every fold), ``cv_best.tsv`` (one row per
+target: l2, l1, num_round, score, se) and ``cv_folds.tsv`` (chromosome, fold, rows) go to
+``--output_dir``.  Each target is then trained on all training rows at its choice, and its lines,
+files and metrics are those of a plain run with ``--l2``, ``--l1`` and ``--num_round`` set to it;
+``--cv-only`` stops after the tables.  ``--cv`` with ``--n_bootstrap`` is refused.
+
 Left out: the scatter plots (``train.py:161-184``), ``--kidney_genes_only`` and
 ``--match_with_basenji2`` (the latter reads a hard-coded path of its author's machine).
 ``--annoFile`` is honoured (the reference parses it and reads ``./resources/geneanno.csv``,
@@ -41,10 +53,12 @@ import numpy as np
 import pandas as pd
 
 from .predict import NFEAT, get_keep_mask
-from .xgblinear import ColMatrix, predict_cols, train
+from .xgblinear import ColMatrix, cv, predict_cols, train
 
 
-def build_parser():
+def build_parser(cv: bool = False):
+    """The arguments of the reference CLIs and the additions above; ``cv=True`` (what ``main`` uses) adds
+    the cross-validation flags.  ``run`` treats a namespace without them as cross-validation off."""
     p = argparse.ArgumentParser(description='Process some integers.')
     p.add_argument('--targetIndex', action="store", dest="targetIndex", nargs='+', required=True,
                    help="column(s) of expFile to train on, or 'all'")
@@ -55,7 +69,21 @@ def build_parser():
                    help="chromosomes taken out of the training rows (train_susztak.py holds out chr7)")
     p.add_argument('--metrics', action='store_true', default=False,
                    help="score every model on its train and test rows; write metrics/metrics.h5 and metrics.tsv")
+    if cv:
+        add_cv_arguments(p)
     return p
+
+
+def add_cv_arguments(p):
+    """The cross-validation flags (module docstring), all off by default."""
+    p.add_argument('--cv', type=int, default=0, metavar='K',
+                   help="choose l2, l1 and the number of rounds per target by K-fold cross-validation over "
+                        "whole chromosomes (0: off)")
+    p.add_argument('--l2-grid', dest='l2_grid', type=float, nargs='+', default=None, help="default: --l2 alone")
+    p.add_argument('--l1-grid', dest='l1_grid', type=float, nargs='+', default=None, help="default: --l1 alone")
+    p.add_argument('--cv-rule', dest='cv_rule', choices=('min', '1se'), default='min')
+    p.add_argument('--cv-only', dest='cv_only', action='store_true', default=False,
+                   help="write the cross-validation tables and train nothing further")
 
 
 def add_reference_arguments(p):
@@ -114,6 +142,74 @@ def bootstrap_weights(train_mask: np.ndarray, seed: int) -> np.ndarray:
     return np.bincount(draw, minlength=train_mask.shape[0])
 
 
+def chromosome_folds(seqnames, K: int):
+    """K folds of whole chromosomes over rows named by ``seqnames``: the chromosomes by row count
+    descending, then name, each to the fold with the fewest rows so far (the lowest index on a tie).
+    Returns (fold int64 per row, [(chromosome, fold, rows)] in that order)."""
+    seqnames = np.asarray(seqnames, dtype=str)
+    names, counts = np.unique(seqnames, return_counts=True)
+    if K < 2:
+        raise ValueError("--cv needs at least 2 folds")
+    if len(names) < K:
+        raise ValueError(f"--cv {K}: the training rows span only {len(names)} chromosomes")
+    order = sorted(zip(names.tolist(), counts.tolist()), key=lambda c: (-c[1], c[0]))
+    size, fold_of = [0] * K, {}
+    for name, rows in order:
+        k = min(range(K), key=lambda i: (size[i], i))
+        fold_of[name] = k
+        size[k] += rows
+    fold = np.array([fold_of[s] for s in seqnames.tolist()], dtype=np.int64)
+    return fold, [(name, fold_of[name], rows) for name, rows in order]
+
+
+def penalty_grid(l2s, l1s) -> list:
+    """The product of the two lists as (l2, l1) pairs, by descending l2, then descending l1: from the
+    most to the least regularised, the order ``--cv-rule 1se`` prefers."""
+    return sorted(((float(a), float(b)) for a in l2s for b in l1s), key=lambda p: (-p[0], -p[1]))
+
+
+def check_cv_args(args) -> None:
+    """Refuse flag combinations that cross-validation does not cover, before any file is read."""
+    K = int(getattr(args, 'cv', 0) or 0)
+    if K == 0:
+        for flag in ('l2_grid', 'l1_grid'):
+            if getattr(args, flag, None) is not None:
+                raise ValueError(f"--{flag.replace('_', '-')} needs --cv")
+        if getattr(args, 'cv_only', False) or getattr(args, 'cv_rule', 'min') != 'min':
+            raise ValueError("--cv-rule and --cv-only need --cv")
+        return
+    if K < 2:
+        raise ValueError("--cv needs at least 2 folds")
+    if args.n_bootstrap > 0:
+        raise ValueError("--cv with --n_bootstrap is not supported: cross-validate first, then bootstrap at the "
+                         "chosen --l2, --l1 and --num_round")
+    if args.num_round < 1:
+        raise ValueError("--cv needs --num_round >= 1")
+
+
+def write_cv_tables(output_dir: str, K: int, rows: list, folds: list) -> None:
+    """cv.tsv, cv_best.tsv and cv_folds.tsv.  rows: (target name, CVResult, index of the target in
+    it) per target; folds: (target names, chromosome table) per group of targets sharing rows."""
+    with open(f'{output_dir}/cv.tsv', 'w') as f, open(f'{output_dir}/cv_best.tsv', 'w') as fb:
+        f.write('\t'.join(['target', 'l2', 'l1', 'round', 'score', 'se'] + [f'fold{k}' for k in range(K)]) + '\n')
+        fb.write('\t'.join(['target', 'l2', 'l1', 'num_round', 'score', 'se']) + '\n')
+        for name, res, t in rows:
+            for g, (l2, l1) in enumerate(res.grid):
+                for r in range(res.score.shape[2]):
+                    f.write('\t'.join([str(name), repr(float(l2)), repr(float(l1)), str(r + 1)] + [
+                        '%.17g' % v for v in (res.score[t, g, r], res.se[t, g, r], *res.heldout[t, g, :, r])]) + '\n')
+            g, r = int(res.best_g[t]), int(res.best_round[t])
+            fb.write('\t'.join([str(name), repr(float(res.grid[g, 0])), repr(float(res.grid[g, 1])), str(r),
+                                '%.17g' % res.score[t, g, r - 1], '%.17g' % res.se[t, g, r - 1]]) + '\n')
+    with open(f'{output_dir}/cv_folds.tsv', 'w') as f:
+        f.write('chromosome\tfold\trows\n')
+        for names, table in folds:
+            if len(folds) > 1:                         # targets whose finite-log filters differ have their own rows
+                f.write('# targets: ' + ','.join(str(n) for n in names) + '\n')
+            for chrom, k, n in table:
+                f.write(f'{chrom}\t{k}\t{n}\n')
+
+
 def target_indices(spec, ncols: int) -> list:
     if len(spec) == 1 and spec[0] == 'all':
         return list(range(1, ncols))
@@ -154,6 +250,9 @@ def run(args, model_dir=None) -> list:
     save, dump; with ``--metrics`` also metrics) in the order their lines were printed.  The model
     files go to ``model_dir`` (default: ``args.output_dir``)."""
     holdout, want_metrics = getattr(args, 'holdout', None) or [], bool(getattr(args, 'metrics', False))
+    check_cv_args(args)
+    cv_k = int(getattr(args, 'cv', 0) or 0)
+    cv_rows, cv_fold_tables = [], []
     model_dir = args.output_dir if model_dir is None else model_dir
     os.makedirs(args.output_dir, exist_ok=True)
     os.makedirs(model_dir, exist_ok=True)
@@ -192,8 +291,21 @@ def run(args, model_dir=None) -> list:
         ytr = np.stack([j[2] for j in jobs])
         wtr = np.stack([j[3] for j in jobs]) if args.n_bootstrap > 0 else None
         yte = np.stack([j[4] for j in jobs])
-        models, history = train(Xtr, ytr, wtr, num_round=args.num_round, eta=args.eta, lambda_=args.l2,
-                                alpha=args.l1, base_score=args.base_score, evals=[(Xte, yte)])
+        if cv_k:
+            grid = penalty_grid(args.l2_grid or [args.l2], args.l1_grid or [args.l1])
+            fold, table = chromosome_folds(np.asarray(geneanno['seqnames'])[tr], cv_k)
+            chosen = cv(Xtr, ytr, fold, grid, num_round=args.num_round, eta=args.eta, base_score=args.base_score,
+                        rule=args.cv_rule)
+            cv_rows += [(geneexp.columns[ti], chosen, t) for t, ti in enumerate(tis)]
+            cv_fold_tables.append(([geneexp.columns[ti] for ti in tis], table))
+            if args.cv_only:
+                continue
+            models, history = chosen.refit(Xtr, ytr, evals=[(Xte, yte)], with_history=True)
+            settings = [(float(chosen.grid[g, 0]), int(r)) for g, r in zip(chosen.best_g, chosen.best_round)]
+        else:
+            models, history = train(Xtr, ytr, wtr, num_round=args.num_round, eta=args.eta, lambda_=args.l2,
+                                    alpha=args.l1, base_score=args.base_score, evals=[(Xte, yte)])
+            settings = [(args.l2, args.num_round)] * len(jobs)
         ypred_dev = predict_cols(Xte, models)
         ypred = ypred_dev.cpu().numpy()
         if want_metrics:
@@ -203,15 +315,16 @@ def run(args, model_dir=None) -> list:
         for m, (ti, k, _, _, ytrue) in enumerate(jobs):
             name = geneexp.columns[ti]
             print(f"Cell type: {name}" + ("" if k is None else f" (bootstrap {k})"))
-            for r in range(args.num_round):
-                print("[%d]\teval-rmse:%f\ttrain-rmse:%f" % (r, history[m, r, 1], history[m, r, 0]))
+            l2, num_round = settings[m]
+            for r in range(num_round):
+                print("[%d]\teval-rmse:%f\ttrain-rmse:%f" % (r, history[m][r, 1], history[m][r, 0]))
             print(spearman_line(ypred[m], ytrue))
             tag = "" if k is None else f".boot{k}"
             if args.evalFile != '':
                 path = args.evalFile if len(jobs) == 1 and len(groups) == 1 else f"{args.evalFile}.{name}{tag}"
                 pd.DataFrame({'pred': ypred[m], 'target': ytrue}).to_csv(path)
-            stem = (f'{model_dir}/expecto_{args.filterStr}.pseudocount{args.pseudocount}.lambda{args.l2}'
-                    f'.round{args.num_round}.basescore{args.base_score}.{name}{tag}')
+            stem = (f'{model_dir}/expecto_{args.filterStr}.pseudocount{args.pseudocount}.lambda{l2}'
+                    f'.round{num_round}.basescore{args.base_score}.{name}{tag}')
             models[m].save_legacy(stem + '.save')
             models[m].save_dump(stem + '.dump')
             results.append({"name": name, "boot": k, "model": models[m], "history": history[m],
@@ -220,7 +333,9 @@ def run(args, model_dir=None) -> list:
                 pt, st, rt, pv, sv, rv = (float(v) for v in scores[m])
                 results[-1]["metrics"] = {'pearsonr_trains': pt, 'pearsonr_valids': pv, 'spearmanr_trains': st,
                                           'spearmanr_valids': sv, 'r2_trains': rt, 'r2_valids': rv}
-    if want_metrics:
+    if cv_k:
+        write_cv_tables(args.output_dir, cv_k, cv_rows, cv_fold_tables)
+    if want_metrics and not (cv_k and args.cv_only):
         write_metrics(args.output_dir, results)
     return results
 
@@ -228,7 +343,7 @@ def run(args, model_dir=None) -> list:
 def main(argv=None):
     import torch
 
-    args = build_parser().parse_args(argv)
+    args = build_parser(cv=True).parse_args(argv)
     if not torch.cuda.is_available():
         raise RuntimeError("expecto_amd.train needs a GPU (HIP); there is no CPU path")
     return run(args)

@@ -33,6 +33,7 @@
  *   expecto_gblinear_predict       xgboost gblinear scoring of feature rows (predict.py:150-166)
  *   expecto_gblinear_train_round   one xgb.train boosting round of gblinear / reg:linear models
  *                                  (train.py:140-146, train_bootstrap.py:88-106)
+ *   expecto_gblinear_train_round_hp  the same round with eta / lambda / alpha / lambda_bias per model
  *   expecto_gblinear_predict_cols  bst.predict(dtrain / dtest) on the training matrix (train.py:147)
  *   expecto_gblinear_rmse          the eval-rmse / train-rmse of xgb.train's evallist (train.py:144-146)
  *   expecto_shift_reduce           200-shift reduction of consensus / eQTL sequences
@@ -404,6 +405,17 @@ int expecto_gblinear_train_round(const float* X, long long ld, int n, int num_fe
                                  long long y_stride, const float* h, long long h_stride, float* w, double* sh,
                                  int first, double eta, double lambda, double alpha, double lambda_bias,
                                  float base_score, float* pred, void* stream);
+
+/* The same round with hyper-parameters per model: hyper is a DEVICE array [n_models, 4] of doubles,
+ * row m = (eta, lambda, alpha, lambda_bias) of model m (a grid of penalties times cross-validation
+ * folds is one batch over one X).  Everything else -- arguments, checks, the row cap, the
+ * arithmetic and so the bits -- is expecto_gblinear_train_round's: model m of this call equals
+ * that entry point run with row m's scalars.  hyper NULL is EXPECTO_EINVAL.  The values are not
+ * validated here (a NaN or negative penalty gives that model NaN or diverging weights and leaves
+ * every other model of the batch alone); expecto_amd.xgblinear.train checks them. */
+int expecto_gblinear_train_round_hp(const float* X, long long ld, int n, int num_feature, int n_models, const float* y,
+                                    long long y_stride, const float* h, long long h_stride, float* w, double* sh,
+                                    int first, const double* hyper, float base_score, float* pred, void* stream);
 
 /* out[m, i] = float32(bias_m + base_score) + sum_j X[j*ld + i] * w_m[j], in float32 in column
  * order with every product and sum rounded separately (expecto_gblinear_predict's rule on the
