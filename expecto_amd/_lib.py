@@ -206,3 +206,82 @@ def dptr(t) -> int:
     if not t.is_cuda:
         raise RuntimeError("expecto_amd kernels need device (HIP) tensors; there is no CPU path")
     return int(t.data_ptr())
+
+
+# ---- the device-call layer of the analysis modules (INTEGRATION.md "Binding helpers") ----------
+
+def require_gpu(module: str, what: str = ""):
+    """torch, or the RuntimeError of a module that has no CPU path."""
+    import torch
+
+    if not torch.cuda.is_available():
+        raise RuntimeError(f"expecto_amd.{module} needs a GPU (HIP){what}; there is no CPU path")
+    return torch
+
+
+def device_of(device=None):
+    """The given device as a ``torch.device``, or else the current HIP device."""
+    import torch
+
+    return torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+
+
+def call(name: str, *args, what: str | None = None) -> None:
+    """``name(*args, stream)`` on torch's current stream; RuntimeError with the library's message on a
+    non-zero status.  ``what``: the label of the message where a call site's differs from ``name``."""
+    lib = load()
+    st = getattr(lib, name)(*args, stream_ptr())
+    if st != 0:
+        raise RuntimeError(f"{what or name} failed (status {st}): {lib.expecto_last_error().decode()}")
+
+
+def host_call(name: str, *args, prefix: bool = True) -> None:
+    """``name(*args)`` of an entry point that takes no stream; ValueError with the library's message,
+    after ``name: `` unless ``prefix`` is false."""
+    lib = load()
+    if getattr(lib, name)(*args) != 0:
+        msg = lib.expecto_last_error().decode()
+        raise ValueError(f"{name}: {msg}" if prefix else msg)
+
+
+def upload(array, dev):
+    """A host array as a tensor on ``dev``."""
+    import numpy as np
+    import torch
+
+    return torch.from_numpy(np.ascontiguousarray(array)).to(dev)
+
+
+def workspace(nbytes: int, dev):
+    """A float64 tensor of at least ``nbytes`` bytes on ``dev``."""
+    import torch
+
+    return torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
+
+
+class EventTimer:
+    """Event-timed device milliseconds for a ``timings`` dict; with ``timings`` None every method does
+    nothing and no event exists.  ``mark()`` records an event on the current stream; interval ``i`` lies
+    between marks ``i`` and ``i + 1`` and must have completed (a copy to the host, or ``mark(sync=True)``)
+    before ``set`` or ``add`` reads it."""
+
+    def __init__(self, timings):
+        self.timings, self.events = timings, []
+
+    def mark(self, sync: bool = False) -> None:
+        if self.timings is None:
+            return
+        import torch
+
+        self.events.append(torch.cuda.Event(enable_timing=True))
+        self.events[-1].record()
+        if sync:
+            self.events[-1].synchronize()
+
+    def set(self, key: str, i: int = 0) -> None:
+        if self.timings is not None:
+            self.timings[key] = self.events[i].elapsed_time(self.events[i + 1])
+
+    def add(self, key: str, i: int = 0) -> None:
+        if self.timings is not None:
+            self.timings[key] = self.timings.get(key, 0.0) + self.events[i].elapsed_time(self.events[i + 1])

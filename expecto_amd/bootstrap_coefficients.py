@@ -111,11 +111,10 @@ def run(args) -> dict:
 
 
 def main(argv=None):
-    import torch
+    from . import _lib
 
     args = build_parser().parse_args(argv)
-    if not torch.cuda.is_available():
-        raise RuntimeError("expecto_amd.bootstrap_coefficients needs a GPU (HIP); there is no CPU path")
+    _lib.require_gpu("bootstrap_coefficients")
     return run(args)
 
 

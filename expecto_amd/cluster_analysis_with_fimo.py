@@ -274,23 +274,13 @@ def csr(matches):
     return ptr, np.array(flat, np.int32).reshape(-1)
 
 
-def _call(lib, name, *args):
-    from . import _lib
-    st = getattr(lib, name)(*args, _lib.stream_ptr())
-    if st != 0:
-        raise RuntimeError(f"{name} failed (status {st}): {lib.expecto_last_error().decode()}")
-
-
 def device_counts(contrib, set_bits, M, seq_ptr, motif_idx, batch: Batch, n_neg, T, device=None, timings=None):
     """One ``expecto_cluster_enrich`` call.  ``contrib``: float64 [V, C] on the host, or a float64 device
     tensor [V, >= C] with unit column stride (used in place).  Returns pos_matches [P, T], pos_motifs
     [P, T], neg [P, 2] (int64) and min_rank int32 [P, C].  ``timings`` adds ``upload_ms`` (host clock
     around the copies, synchronised) and ``enrich_ms`` (device events)."""
-    import torch
-
     from . import _lib
-    if not torch.cuda.is_available():
-        raise RuntimeError("expecto_amd.cluster_analysis_with_fimo needs a GPU (HIP); there is no CPU path")
+    torch = _lib.require_gpu("cluster_analysis_with_fimo")
     lib = _lib.load()
     C = int(set_bits.shape[0])
     P = int(batch.table.shape[0])
@@ -302,7 +292,7 @@ def device_counts(contrib, set_bits, M, seq_ptr, motif_idx, batch: Batch, n_neg,
         V, ld = int(contrib.shape[0]), int(contrib.stride(0)) if contrib.shape[0] > 1 else int(contrib.shape[1])
     else:
         contrib = np.ascontiguousarray(contrib, np.float64)
-        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        dev = _lib.device_of(device)
         V, ld = contrib.shape
     empty = (np.zeros((P, T), np.int64), np.zeros((P, T), np.int64), np.zeros((P, 2), np.int64),
              np.full((P, C), C, np.int32))
@@ -312,57 +302,53 @@ def device_counts(contrib, set_bits, M, seq_ptr, motif_idx, batch: Batch, n_neg,
     seq_ptr = np.ascontiguousarray(seq_ptr, np.int64)
     with torch.cuda.device(dev):
         t0 = time.perf_counter()
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        up = lambda a: _lib.upload(a, dev)
         cd = contrib if torch.is_tensor(contrib) else up(contrib)
         bits_d, ptr_d, idx_d, tab_d = up(set_bits.view(np.int64)), up(seq_ptr), up(motif_idx), up(table)
         perms_d, sids_d, rows_d = up(batch.perms.view(np.int16)), up(batch.sids), up(batch.rows)
         nbytes = int(lib.expecto_cluster_enrich_workspace(S, C))
-        ws = torch.empty(max(1, (nbytes + 3) // 4), dtype=torch.int32, device=dev)
+        ws = _lib.workspace(max(nbytes, 4), dev)
         pos_m = torch.empty((P, T), dtype=torch.int64, device=dev)
         pos_b = torch.empty((P, T), dtype=torch.int64, device=dev)
         neg = torch.empty((P, 2), dtype=torch.int64, device=dev)
         min_rank = torch.empty((P, C), dtype=torch.int32, device=dev)
         torch.cuda.synchronize(dev)
         t1 = time.perf_counter()
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-        ev[0].record()
-        _call(lib, "expecto_cluster_enrich", cd.data_ptr(), V, C, ld, bits_d.data_ptr(), int(M), seq_ptr.ctypes.data,
-              ptr_d.data_ptr(), idx_d.data_ptr() if idx_d.numel() else None, S, table.ctypes.data, tab_d.data_ptr(), P,
-              perms_d.data_ptr() if perms_d.numel() else None, int(batch.perms.shape[0]), sids_d.data_ptr(),
-              int(batch.sids.shape[0]), rows_d.data_ptr(), int(batch.rows.shape[0]), int(n_neg), int(T),
-              pos_m.data_ptr(), pos_b.data_ptr(), neg.data_ptr(), min_rank.data_ptr(), ws.data_ptr(), max(nbytes, 4))
-        ev[1].record()
+        timer = _lib.EventTimer(timings)
+        timer.mark()
+        _lib.call("expecto_cluster_enrich", cd.data_ptr(), V, C, ld, bits_d.data_ptr(), int(M), seq_ptr.ctypes.data,
+                  ptr_d.data_ptr(), idx_d.data_ptr() if idx_d.numel() else None, S, table.ctypes.data,
+                  tab_d.data_ptr(), P, perms_d.data_ptr() if perms_d.numel() else None, int(batch.perms.shape[0]),
+                  sids_d.data_ptr(), int(batch.sids.shape[0]), rows_d.data_ptr(), int(batch.rows.shape[0]),
+                  int(n_neg), int(T), pos_m.data_ptr(), pos_b.data_ptr(), neg.data_ptr(), min_rank.data_ptr(),
+                  ws.data_ptr(), max(nbytes, 4))
+        timer.mark()
         out = (pos_m.cpu().numpy(), pos_b.cpu().numpy(), neg.cpu().numpy(), min_rank.cpu().numpy())
         if timings is not None:
             timings["upload_ms"] = timings.get("upload_ms", 0.0) + 1e3 * (t1 - t0)
-            timings["enrich_ms"] = timings.get("enrich_ms", 0.0) + ev[0].elapsed_time(ev[1])
+        timer.add("enrich_ms")
     return out
 
 
 def device_sf(k, M, n, N, device=None, timings=None):
     """``scipy.stats.hypergeom.sf(k - 1, M, n, N)`` of int64 arrays of one shape, by one
     ``expecto_hypergeom_sf`` call.  ``timings`` adds ``sf_ms`` (device events)."""
-    import torch
-
     from . import _lib
-    if not torch.cuda.is_available():
-        raise RuntimeError("expecto_amd.cluster_analysis_with_fimo needs a GPU (HIP); there is no CPU path")
-    lib = _lib.load()
+    torch = _lib.require_gpu("cluster_analysis_with_fimo")
     k = np.ascontiguousarray(k, np.int64)
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    dev = _lib.device_of(device)
     if k.size == 0:
         return np.zeros(k.shape, np.float64)
     with torch.cuda.device(dev):
-        q = torch.from_numpy(np.stack([k.ravel()] + [np.ascontiguousarray(a, np.int64).ravel() for a in (M, n, N)])).to(dev)
+        q = _lib.upload(np.stack([k.ravel()] + [np.ascontiguousarray(a, np.int64).ravel() for a in (M, n, N)]), dev)
         out = torch.empty(k.size, dtype=torch.float64, device=dev)
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-        ev[0].record()
-        _call(lib, "expecto_hypergeom_sf", q[0].data_ptr(), q[1].data_ptr(), q[2].data_ptr(), q[3].data_ptr(), k.size,
-              out.data_ptr())
-        ev[1].record()
+        timer = _lib.EventTimer(timings)
+        timer.mark()
+        _lib.call("expecto_hypergeom_sf", q[0].data_ptr(), q[1].data_ptr(), q[2].data_ptr(), q[3].data_ptr(), k.size,
+                  out.data_ptr())
+        timer.mark()
         res = out.cpu().numpy().reshape(k.shape)
-        if timings is not None:
-            timings["sf_ms"] = timings.get("sf_ms", 0.0) + ev[0].elapsed_time(ev[1])
+        timer.add("sf_ms")
     return res
 
 

@@ -107,13 +107,10 @@ def run_problems(X, problems, tol, max_iter, device=None, timings=None):
     ``expecto_kmeans_plusplus`` and one ``expecto_kmeans_lloyd`` call.  Returns per problem
     ``(labels, centres, inertia, n_iter, seeds)``.  ``timings``: a dict that receives the two calls'
     device times in ms (``seeding_ms``, ``lloyd_ms``), measured with events."""
-    import torch
-
     from . import _lib
-    if not torch.cuda.is_available():
-        raise RuntimeError("expecto_amd.cluster_and_viz needs a GPU (HIP); there is no CPU path")
+    torch = _lib.require_gpu("cluster_and_viz")
     lib = _lib.load()
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    dev = _lib.device_of(device)
     n, d = X.shape
     P = len(problems)
     if P == 0:
@@ -127,15 +124,8 @@ def run_problems(X, problems, tol, max_iter, device=None, timings=None):
     lloyd_tab = _table([(k, max_iter, c_off[i], c_off[i], i * n) for i, k in enumerate(ks)])
     u = np.concatenate([np.asarray(p[2], np.float64).ravel() for p in problems] + [np.zeros(1)])
     nbytes = int(lib.expecto_kmeans_workspace(n, d, int(ks.max()), int(Ts.max()), P))
-
-    def call(name, *args):
-        st = getattr(lib, name)(*args, _lib.stream_ptr())
-        if st != 0:
-            raise RuntimeError(f"{name} failed (status {st}): {lib.expecto_last_error().decode()}")
-
     with torch.cuda.device(dev):
-        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-        Xd, ud, seed_d, lloyd_d = up(X), up(u), up(seed_tab), up(lloyd_tab)
+        Xd, ud, seed_d, lloyd_d = (_lib.upload(a, dev) for a in (X, u, seed_tab, lloyd_tab))
         told = torch.full((P,), float(tol), dtype=torch.float64, device=dev)
         total = int(c_off[-1])
         idx = torch.empty(total, dtype=torch.int32, device=dev)
@@ -144,24 +134,20 @@ def run_problems(X, problems, tol, max_iter, device=None, timings=None):
         labels = torch.empty((P, n), dtype=torch.int32, device=dev)
         inertia = torch.empty(P, dtype=torch.float64, device=dev)
         n_iter = torch.empty(P, dtype=torch.int32, device=dev)
-        ws = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=dev)
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if timings is not None else None
-        if ev:
-            ev[0].record()
-        call("expecto_kmeans_plusplus", Xd.data_ptr(), n, d, d, P, seed_tab.ctypes.data, seed_d.data_ptr(),
-             ud.data_ptr(), idx.data_ptr(), init.data_ptr(), ws.data_ptr(), nbytes)
-        if ev:
-            ev[1].record()
-        call("expecto_kmeans_lloyd", Xd.data_ptr(), n, d, d, P, lloyd_tab.ctypes.data, lloyd_d.data_ptr(),
-             told.data_ptr(), init.data_ptr(), labels.data_ptr(), centres.data_ptr(), inertia.data_ptr(),
-             n_iter.data_ptr(), ws.data_ptr(), nbytes)
-        if ev:
-            ev[2].record()
+        ws = _lib.workspace(nbytes, dev)
+        timer = _lib.EventTimer(timings)
+        timer.mark()
+        _lib.call("expecto_kmeans_plusplus", Xd.data_ptr(), n, d, d, P, seed_tab.ctypes.data, seed_d.data_ptr(),
+                  ud.data_ptr(), idx.data_ptr(), init.data_ptr(), ws.data_ptr(), nbytes)
+        timer.mark()
+        _lib.call("expecto_kmeans_lloyd", Xd.data_ptr(), n, d, d, P, lloyd_tab.ctypes.data, lloyd_d.data_ptr(),
+                  told.data_ptr(), init.data_ptr(), labels.data_ptr(), centres.data_ptr(), inertia.data_ptr(),
+                  n_iter.data_ptr(), ws.data_ptr(), nbytes)
+        timer.mark()
         idx, centres, labels = idx.cpu().numpy(), centres.cpu().numpy(), labels.cpu().numpy()
         inertia, n_iter = inertia.cpu().numpy(), n_iter.cpu().numpy()
-        if ev:
-            timings["seeding_ms"] = ev[0].elapsed_time(ev[1])
-            timings["lloyd_ms"] = ev[1].elapsed_time(ev[2])
+        timer.set("seeding_ms", 0)
+        timer.set("lloyd_ms", 1)
     return [(labels[i], centres[c_off[i]:c_off[i + 1]].copy(), float(inertia[i]), int(n_iter[i]),
              idx[c_off[i]:c_off[i + 1]].copy()) for i in range(P)]
 
@@ -255,42 +241,31 @@ class _TsneDevice:
     """The device side of one embedding: X's affinities, then chained descent calls on resident buffers."""
 
     def __init__(self, X, perplexity, device=None, timed=False):
-        import torch
-
         from . import _lib
-        if not torch.cuda.is_available():
-            raise RuntimeError("expecto_amd.cluster_and_viz needs a GPU (HIP); there is no CPU path")
-        self.torch, self.lib, self._lib = torch, _lib.load(), _lib
-        self.dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-        self.n, self.timed = X.shape[0], timed
-        self.affinities_ms = self.descent_ms = 0.0
+        torch = _lib.require_gpu("cluster_and_viz")
+        self.torch, self._lib = torch, _lib
+        self.dev = _lib.device_of(device)
+        self.n = X.shape[0]
+        self.ms = {"affinities_ms": 0.0, "descent_ms": 0.0} if timed else None    # summed over this embedding's calls
         n, d = X.shape
-        self.nbytes = int(self.lib.expecto_tsne_workspace(n))
+        self.nbytes = int(_lib.load().expecto_tsne_workspace(n))
         with torch.cuda.device(self.dev):
             f64 = dict(dtype=torch.float64, device=self.dev)
             Xd = torch.from_numpy(X).to(self.dev)
             self.P, self.beta = torch.empty((n, n), **f64), torch.empty(n, **f64)
             self.steps = torch.empty(n, dtype=torch.int32, device=self.dev)
-            self.ws = torch.empty((self.nbytes + 7) // 8, **f64)
+            self.ws = _lib.workspace(self.nbytes, self.dev)
             self.Y, self.update, self.gains = (torch.empty((n, 2), **f64) for _ in range(3))
             self.stats = torch.zeros(3, **f64)
-            self.affinities_ms = self._call("expecto_tsne_affinities", Xd.data_ptr(), n, d, d, perplexity,
-                                            self.P.data_ptr(), self.beta.data_ptr(), self.steps.data_ptr(),
-                                            self.ws.data_ptr(), self.nbytes)
+            self._timed("affinities_ms", "expecto_tsne_affinities", Xd.data_ptr(), n, d, d, perplexity,
+                        self.P.data_ptr(), self.beta.data_ptr(), self.steps.data_ptr(), self.ws.data_ptr(), self.nbytes)
 
-    def _call(self, name, *args):
-        torch = self.torch
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)] if self.timed else None
-        if ev:
-            ev[0].record()
-        st = getattr(self.lib, name)(*args, self._lib.stream_ptr())
-        if st != 0:
-            raise RuntimeError(f"{name} failed (status {st}): {self.lib.expecto_last_error().decode()}")
-        if ev:
-            ev[1].record()
-            ev[1].synchronize()
-            return ev[0].elapsed_time(ev[1])
-        return 0.0
+    def _timed(self, key, name, *args):
+        timer = self._lib.EventTimer(self.ms)
+        timer.mark()
+        self._lib.call(name, *args)
+        timer.mark(sync=True)
+        timer.add(key)
 
     def start(self, Y0):
         with self.torch.cuda.device(self.dev):
@@ -303,10 +278,9 @@ class _TsneDevice:
     def descend(self, exaggeration, momentum, learning_rate, n_iter):
         """n_iter iterations; returns the call's (error, grad_norm, Z)."""
         with self.torch.cuda.device(self.dev):
-            self.descent_ms += self._call("expecto_tsne_descend", self.P.data_ptr(), self.n, float(exaggeration),
-                                          self.Y.data_ptr(), self.update.data_ptr(), self.gains.data_ptr(),
-                                          float(momentum), float(learning_rate), int(n_iter), 1,
-                                          self.stats.data_ptr(), self.ws.data_ptr(), self.nbytes)
+            self._timed("descent_ms", "expecto_tsne_descend", self.P.data_ptr(), self.n, float(exaggeration),
+                        self.Y.data_ptr(), self.update.data_ptr(), self.gains.data_ptr(), float(momentum),
+                        float(learning_rate), int(n_iter), 1, self.stats.data_ptr(), self.ws.data_ptr(), self.nbytes)
             return self.stats.cpu().numpy()
 
 
@@ -363,7 +337,7 @@ def tsne(X, perplexity=30.0, early_exaggeration=12.0, learning_rate='auto', max_
                 if grad_norm <= min_grad_norm:
                     break
     if timings is not None:
-        timings["affinities_ms"], timings["descent_ms"] = t.affinities_ms, t.descent_ms
+        timings.update(t.ms)
     return TSNEResult(t.Y.cpu().numpy(), kl, done, t.beta.cpu().numpy())
 
 

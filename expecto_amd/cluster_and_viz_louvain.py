@@ -67,55 +67,24 @@ def _checked(X, k_neighbors):
     return X, k
 
 
-def _device(device):
-    import torch
-
-    from . import _lib
-    if not torch.cuda.is_available():
-        raise RuntimeError("expecto_amd.cluster_and_viz_louvain needs a GPU (HIP); there is no CPU path")
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
-    return torch, _lib, _lib.load(), dev
-
-
-def _call(lib, _lib, name, *args):
-    st = getattr(lib, name)(*args, _lib.stream_ptr())
-    if st != 0:
-        raise RuntimeError(f"{name} failed (status {st}): {lib.expecto_last_error().decode()}")
-
-
-class _Timer:
-    """Event-timed device ms of the calls between ``start`` and ``stop``, if a dict wants them."""
-
-    def __init__(self, torch, timings):
-        self.timings = timings
-        self.ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)] if timings is not None else None
-
-    def start(self):
-        if self.ev:
-            self.ev[0].record()
-
-    def stop(self, key):
-        if self.ev:
-            self.ev[1].record()
-            self.ev[1].synchronize()
-            self.timings[key] = self.ev[0].elapsed_time(self.ev[1])
-
-
 def knn_graph(X, k_neighbors=K_NEIGHBORS, device=None, timings=None):
     """``expecto_knn_jaccard`` of X: (nbr int32 [n, k], w float64 [n, k]) as host arrays.  ``nbr[i]`` is
     ``NearestNeighbors(n_neighbors=k).fit(X).kneighbors(X)[1][i]`` with ties to the lower index; ``w`` the
     Jaccard index of the two neighbour sets, 0 where a point is its own neighbour."""
     X, k = _checked(X, k_neighbors)
-    torch, _lib, lib, dev = _device(device)
+    from . import _lib
+    torch = _lib.require_gpu("cluster_and_viz_louvain")
+    dev = _lib.device_of(device)
     n, d = X.shape
     with torch.cuda.device(dev):
-        Xd = torch.from_numpy(X).to(dev)
+        Xd = _lib.upload(X, dev)
         nbr = torch.empty((n, k), dtype=torch.int32, device=dev)
         w = torch.empty((n, k), dtype=torch.float64, device=dev)
-        timer = _Timer(torch, timings)
-        timer.start()
-        _call(lib, _lib, "expecto_knn_jaccard", Xd.data_ptr(), n, d, d, k, nbr.data_ptr(), w.data_ptr())
-        timer.stop("graph_ms")
+        timer = _lib.EventTimer(timings)
+        timer.mark()
+        _lib.call("expecto_knn_jaccard", Xd.data_ptr(), n, d, d, k, nbr.data_ptr(), w.data_ptr())
+        timer.mark(sync=True)
+        timer.set("graph_ms")
         return nbr.cpu().numpy(), w.cpu().numpy()
 
 
@@ -141,7 +110,9 @@ def run_problems(indptr, indices, weights, gammas, perms, max_passes=100, max_le
     """``expecto_louvain`` of the CSR graph for the problems ``(gammas[p], perms[p])`` in one launch.
     Returns per problem ``(labels, modularity, n_communities, n_levels, n_passes, flags)``.  ``timings``
     receives the launch's device ms (``louvain_ms``)."""
-    torch, _lib, lib, dev = _device(device)
+    from . import _lib
+    torch = _lib.require_gpu("cluster_and_viz_louvain")
+    dev = _lib.device_of(device)
     indptr = np.ascontiguousarray(indptr, np.int32)
     indices = np.ascontiguousarray(indices, np.int32)
     weights = np.ascontiguousarray(weights, np.float64)
@@ -154,20 +125,20 @@ def run_problems(indptr, indices, weights, gammas, perms, max_passes=100, max_le
         raise ValueError("louvain: a resolution is NaN or infinite")
     if P == 0:
         return []
-    nbytes = int(lib.expecto_louvain_workspace(n, nnz, P))
+    nbytes = int(_lib.load().expecto_louvain_workspace(n, nnz, P))
     with torch.cuda.device(dev):
-        up = lambda a: torch.from_numpy(a).to(dev)
-        d_ptr, d_idx, d_w, d_g, d_perm = up(indptr), up(indices), up(weights), up(gammas), up(perms)
+        d_ptr, d_idx, d_w, d_g, d_perm = (_lib.upload(a, dev) for a in (indptr, indices, weights, gammas, perms))
         labels = torch.empty((P, n), dtype=torch.int32, device=dev)
         modularity = torch.empty(P, dtype=torch.float64, device=dev)
         counters = torch.empty((P, 4), dtype=torch.int32, device=dev)
-        ws = torch.empty((nbytes + 7) // 8 + 1, dtype=torch.float64, device=dev)
-        timer = _Timer(torch, timings)
-        timer.start()
-        _call(lib, _lib, "expecto_louvain", d_ptr.data_ptr(), d_idx.data_ptr(), d_w.data_ptr(), n, nnz, P,
-              d_g.data_ptr(), d_perm.data_ptr(), int(max_passes), int(max_levels), labels.data_ptr(),
-              modularity.data_ptr(), counters.data_ptr(), ws.data_ptr(), nbytes)
-        timer.stop("louvain_ms")
+        ws = _lib.workspace(nbytes + 8, dev)
+        timer = _lib.EventTimer(timings)
+        timer.mark()
+        _lib.call("expecto_louvain", d_ptr.data_ptr(), d_idx.data_ptr(), d_w.data_ptr(), n, nnz, P,
+                  d_g.data_ptr(), d_perm.data_ptr(), int(max_passes), int(max_levels), labels.data_ptr(),
+                  modularity.data_ptr(), counters.data_ptr(), ws.data_ptr(), nbytes)
+        timer.mark(sync=True)
+        timer.set("louvain_ms")
         labels, modularity, counters = labels.cpu().numpy(), modularity.cpu().numpy(), counters.cpu().numpy()
     if (counters[:, 3] & BAD_GRAPH).any():
         raise ValueError("louvain: the graph is not a CSR matrix over n nodes, or an order is not a permutation")

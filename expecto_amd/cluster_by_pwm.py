@@ -257,41 +257,23 @@ def compare(motifs, min_w: int = 5, pseudo: float = 1.0, device=None, timings=No
     freq, col_ptr = frequencies(motifs, pseudo)
     if int(min_w) < 1:
         raise ValueError("min_w must be at least 1")
-    import torch
-
     from . import _lib
-    if not torch.cuda.is_available():
-        raise RuntimeError("expecto_amd.cluster_by_pwm needs a GPU (HIP); there is no CPU path")
-    lib = _lib.load()
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    torch = _lib.require_gpu("cluster_by_pwm")
+    dev = _lib.device_of(device)
     M = len(col_ptr) - 1
     npair = M * (M - 1) // 2
     with torch.cuda.device(dev):
-        d_freq = torch.from_numpy(freq).to(dev)
-        d_ptr = torch.from_numpy(col_ptr).to(dev)
+        d_freq, d_ptr = _lib.upload(freq, dev), _lib.upload(col_ptr, dev)
         f64 = [torch.empty(npair, dtype=torch.float64, device=dev) for _ in range(3)]
         i32 = [torch.empty(npair, dtype=torch.int32, device=dev) for _ in range(3)]
-        ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)] if timings is not None else None
-        if ev:
-            ev[0].record()
-        st = lib.expecto_pwm_compare(d_freq.data_ptr(), col_ptr.ctypes.data, d_ptr.data_ptr(), M, int(min_w),
-                                     *[t.data_ptr() for t in f64 + i32], _lib.stream_ptr())
-        if st != 0:
-            raise RuntimeError(f"expecto_pwm_compare failed (status {st}): {lib.expecto_last_error().decode()}")
-        if ev:
-            ev[1].record()
+        timer = _lib.EventTimer(timings)
+        timer.mark()
+        _lib.call("expecto_pwm_compare", d_freq.data_ptr(), col_ptr.ctypes.data, d_ptr.data_ptr(), M, int(min_w),
+                  *[t.data_ptr() for t in f64 + i32])
+        timer.mark()
         out = [t.cpu().numpy() for t in f64 + i32]
-        if ev:
-            timings["compare_ms"] = ev[0].elapsed_time(ev[1])
+        timer.set("compare_ms")
     return Comparison(*out)
-
-
-def _host_call(name, *args):
-    from . import _lib
-    lib = _lib.load()
-    st = getattr(lib, name)(*args)
-    if st != 0:
-        raise ValueError(f"{name}: {lib.expecto_last_error().decode()}")
 
 
 def linkage(dist) -> Tree:
@@ -301,7 +283,9 @@ def linkage(dist) -> Tree:
         raise ValueError("linkage: a condensed distance vector is 1-D")
     n = _n_of_condensed(D.size)
     children, heights, sizes = np.empty((n - 1, 2), np.int32), np.empty(n - 1, np.float64), np.empty(n - 1, np.int32)
-    _host_call("expecto_average_linkage", D.ctypes.data, n, children.ctypes.data, heights.ctypes.data, sizes.ctypes.data)
+    from . import _lib
+    _lib.host_call("expecto_average_linkage", D.ctypes.data, n, children.ctypes.data, heights.ctypes.data,
+                   sizes.ctypes.data)
     return Tree(children, heights, sizes)
 
 
@@ -316,8 +300,9 @@ def threshold_cut(tree, cor, ncor, min_cor: float = 0.6, min_ncor: float = 0.4) 
     if cor.shape != (n * (n - 1) // 2,) or ncor.shape != cor.shape:
         raise ValueError(f"threshold_cut: cor and ncor must hold the {n * (n - 1) // 2} pairs of {n} leaves")
     labels, mean_cor, mean_ncor = np.empty(n, np.int32), np.empty(n - 1, np.float64), np.empty(n - 1, np.float64)
-    _host_call("expecto_linkage_threshold_cut", children.ctypes.data, n, cor.ctypes.data, ncor.ctypes.data,
-               float(min_cor), float(min_ncor), labels.ctypes.data, mean_cor.ctypes.data, mean_ncor.ctypes.data)
+    from . import _lib
+    _lib.host_call("expecto_linkage_threshold_cut", children.ctypes.data, n, cor.ctypes.data, ncor.ctypes.data,
+                   float(min_cor), float(min_ncor), labels.ctypes.data, mean_cor.ctypes.data, mean_ncor.ctypes.data)
     return Cut(labels, mean_cor, mean_ncor)
 
 

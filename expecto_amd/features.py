@@ -31,27 +31,25 @@ def tss_pos_weights(shifts=TSS_SHIFTS) -> np.ndarray:
 
 def tss_reduce(fwd: torch.Tensor, rc: torch.Tensor, weights: torch.Tensor, out: torch.Tensor | None = None):
     """fwd, rc: [G, S, F] fp32 (device); weights [10, S] fp64 (device) -> [G, 10*F] fp64."""
-    lib = _lib.load()
     G, S, F = fwd.shape
     if rc.shape != fwd.shape or weights.shape != (10, S):
         raise RuntimeError("tss_reduce: shape mismatch")
     fwd, rc, weights = fwd.contiguous(), rc.contiguous(), weights.contiguous()
     if out is None:
         out = torch.empty((G, 10 * F), dtype=torch.float64, device=fwd.device)
-    _lib.check(lib.expecto_tss_reduce(_lib.dptr(fwd), _lib.dptr(rc), _lib.dptr(weights), G, S, F,
-                                      _lib.dptr(out), _lib.stream_ptr()), "tss_reduce")
+    _lib.call("expecto_tss_reduce", _lib.dptr(fwd), _lib.dptr(rc), _lib.dptr(weights), G, S, F, _lib.dptr(out),
+              what="tss_reduce")
     return out
 
 
 def fwd_rc_average(x: torch.Tensor, out: torch.Tensor | None = None):
     """[2N, F] fp32 -> [N, F]: (x[:N] + x[N:]) / 2 (predict.py:186)."""
-    lib = _lib.load()
     x = x.contiguous()
     n = x.shape[0] // 2
     F = x.shape[1]
     if out is None:
         out = torch.empty((n, F), dtype=x.dtype, device=x.device)
-    _lib.check(lib.expecto_fwd_rc_average(_lib.dptr(x), n, F, _lib.dptr(out), _lib.stream_ptr()), "fwd_rc_average")
+    _lib.call("expecto_fwd_rc_average", _lib.dptr(x), n, F, _lib.dptr(out), what="fwd_rc_average")
     return out
 
 
@@ -74,7 +72,6 @@ def variant_tables(dist, strand_plus, shifts, device) -> tuple:
 def variant_reduce(effects: torch.Tensor, tables: tuple, out: torch.Tensor | None = None):
     """``variant_features`` on tables already resident (``variant_tables``): one launch per
     65,535 variants (the grid's y limit)."""
-    lib = _lib.load()
     S, n, F = effects.shape
     d, sp, sh, lut = tables
     if d.shape != (n,) or sp.shape != (n,) or sh.shape != (S,):
@@ -85,9 +82,9 @@ def variant_reduce(effects: torch.Tensor, tables: tuple, out: torch.Tensor | Non
     for v0 in range(0, n, 65535):
         v1 = min(n, v0 + 65535)
         eff = effects[:, v0:v1].contiguous() if (v0 or v1 != n) else effects
-        _lib.check(lib.expecto_variant_reduce_lut(_lib.dptr(eff), _lib.dptr(d[v0:v1]), _lib.dptr(sp[v0:v1]),
-                                                  _lib.dptr(sh), S, v1 - v0, F, _lib.dptr(lut), lut.shape[1],
-                                                  _lib.dptr(out[v0:v1]), _lib.stream_ptr()), "variant_reduce")
+        _lib.call("expecto_variant_reduce_lut", _lib.dptr(eff), _lib.dptr(d[v0:v1]), _lib.dptr(sp[v0:v1]),
+                  _lib.dptr(sh), S, v1 - v0, F, _lib.dptr(lut), lut.shape[1], _lib.dptr(out[v0:v1]),
+                  what="variant_reduce")
     return out
 
 
@@ -118,7 +115,6 @@ def variant_contributions(eff_ref: torch.Tensor, eff_alt: torch.Tensor, dist, st
     ``[M, n, n_clu]`` (None without clusters); one launch per 65,535 variants.  outputs: the
     names of the tensors wanted (default: all); the others are neither allocated nor written
     and come back as None."""
-    lib = _lib.load()
     S, n, F = eff_ref.shape
     if eff_alt.shape != eff_ref.shape or eff_ref.dtype != torch.float32 or eff_alt.dtype != torch.float32:
         raise RuntimeError("variant_contributions: eff_ref and eff_alt must be fp32 tensors of one shape")
@@ -163,12 +159,12 @@ def variant_contributions(eff_ref: torch.Tensor, eff_alt: torch.Tensor, dist, st
         whole = v0 == 0 and v1 == n
         er, ea = (eff_ref, eff_alt) if whole else (eff_ref[:, v0:v1].contiguous(), eff_alt[:, v0:v1].contiguous())
         part = out if whole else alloc(v1 - v0)       # the kernel's rows are m * (v1 - v0) + v
-        _lib.check(lib.expecto_variant_contrib(
-            _lib.dptr(er), _lib.dptr(ea), _lib.dptr(d[v0:v1]), _lib.dptr(sp[v0:v1]), _lib.dptr(sh), S, v1 - v0, F,
-            _lib.dptr(lut), lut.shape[1], _lib.dptr(keep_d), nk, _lib.dptr(w), M,
+        _lib.call(
+            "expecto_variant_contrib", _lib.dptr(er), _lib.dptr(ea), _lib.dptr(d[v0:v1]), _lib.dptr(sp[v0:v1]),
+            _lib.dptr(sh), S, v1 - v0, F, _lib.dptr(lut), lut.shape[1], _lib.dptr(keep_d), nk, _lib.dptr(w), M,
             _lib.dptr(ptr_d) if n_clu else None, _lib.dptr(mark_d) if n_clu else None, n_clu,
             optr(part.contrib), optr(part.total), optr(part.prop), optr(part.clu), optr(part.clu_prop),
-            _lib.stream_ptr()), "variant_contrib")
+            what="variant_contrib")
         if not whole:
             for dst, src in zip(out, part):
                 if dst is not None:

@@ -44,7 +44,6 @@ and only the distances are recomputed.  The reference's PNG of the scores is lef
 from __future__ import annotations
 
 import argparse
-import ctypes
 import heapq
 import operator
 import os
@@ -120,13 +119,11 @@ def pairwise_condensed(X, device=None, what="pairwise_condensed"):
         raise ValueError(f"{what}: found {n} point(s), at least 2 are required")
     if not bool(torch.isfinite(t).all()):
         raise ValueError(f"{what}: input X contains NaN or infinity")
-    lib = _lib.load()
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    dev = _lib.device_of(device)
     with torch.cuda.device(dev):
         x = t.to(device=dev, dtype=torch.float64).contiguous()
         cond = torch.empty(n * (n - 1) // 2, dtype=torch.float64, device=dev)
-        _lib.check(lib.expecto_pairwise_euclidean(_lib.dptr(x), n, d, max(d, x.stride(0)), _lib.dptr(cond),
-                                                  _lib.stream_ptr()), "expecto_pairwise_euclidean")
+        _lib.call("expecto_pairwise_euclidean", _lib.dptr(x), n, d, max(d, x.stride(0)), _lib.dptr(cond))
     return cond
 
 
@@ -138,22 +135,20 @@ def ward_tree(X, device=None, return_condensed=False):
     there.  ValueError on fewer than 2 points or a NaN / infinity in ``X``.  With
     ``return_condensed`` the device tensor of the distances (:func:`pairwise_condensed`) is returned
     as a third value; the linkage overwrites its host copy only."""
-    from . import _lib
-
     cond = pairwise_condensed(X, device, "ward_tree")
     n = int(X.shape[0])
-    children, heights = _link(_lib.load(), cond.cpu().numpy(), n)
+    children, heights = _link(cond.cpu().numpy(), n)
     return (children, heights, cond) if return_condensed else (children, heights)
 
 
-def _link(lib, cond: np.ndarray, n: int):
+def _link(cond: np.ndarray, n: int):
+    from . import _lib
+
     children = np.empty((n - 1, 2), np.int32)
     heights = np.empty(n - 1, np.float64)
     sizes = np.empty(n - 1, np.int32)
-    st = lib.expecto_ward_linkage(cond.ctypes.data_as(ctypes.c_void_p), n, children.ctypes.data_as(ctypes.c_void_p),
-                                  heights.ctypes.data_as(ctypes.c_void_p), sizes.ctypes.data_as(ctypes.c_void_p))
-    if st != 0:
-        raise ValueError(lib.expecto_last_error().decode())
+    _lib.host_call("expecto_ward_linkage", cond.ctypes.data, n, children.ctypes.data, heights.ctypes.data,
+                   sizes.ctypes.data, prefix=False)
     return children.astype(np.int64), heights
 
 
@@ -302,7 +297,6 @@ def _run_plan(cond, n: int, plan: SweepPlan) -> np.ndarray:
 
     from . import _lib
 
-    lib = _lib.load()
     dev = cond.device
     n_nodes, n_cuts = len(plan.sizes), len(plan.cut_ptr) - 1
     with torch.cuda.device(dev):
@@ -322,16 +316,13 @@ def _run_plan(cond, n: int, plan: SweepPlan) -> np.ndarray:
         dist = cond
         if square:
             dist = torch.empty((n, n), dtype=torch.float64, device=dev)
-            _lib.check(lib.expecto_square_distances(_lib.dptr(cond), n, _lib.dptr(dist), _lib.stream_ptr()),
-                       "expecto_square_distances")
+            _lib.call("expecto_square_distances", _lib.dptr(cond), n, _lib.dptr(dist))
         S = torch.empty((n_nodes, n), dtype=torch.float64, device=dev)
         samples = torch.empty((n_cuts, n), dtype=torch.float64, device=dev)
-        _lib.check(lib.expecto_silhouette_node_sums(_lib.dptr(dist), int(square), n, plan.node_ptr.ctypes.data,
-                                                    _lib.dptr(node_ptr), _lib.dptr(members), n_nodes, _lib.dptr(S),
-                                                    _lib.stream_ptr()), "expecto_silhouette_node_sums")
-        _lib.check(lib.expecto_silhouette_cuts(_lib.dptr(S), n, n_nodes, _lib.dptr(sizes), plan.cut_ptr.ctypes.data,
-                                               _lib.dptr(cut_ptr), _lib.dptr(active), _lib.dptr(own), n_cuts,
-                                               _lib.dptr(samples), _lib.stream_ptr()), "expecto_silhouette_cuts")
+        _lib.call("expecto_silhouette_node_sums", _lib.dptr(dist), int(square), n, plan.node_ptr.ctypes.data,
+                  _lib.dptr(node_ptr), _lib.dptr(members), n_nodes, _lib.dptr(S))
+        _lib.call("expecto_silhouette_cuts", _lib.dptr(S), n, n_nodes, _lib.dptr(sizes), plan.cut_ptr.ctypes.data,
+                  _lib.dptr(cut_ptr), _lib.dptr(active), _lib.dptr(own), n_cuts, _lib.dptr(samples))
         return samples.cpu().numpy()
 
 
@@ -394,9 +385,8 @@ def training_rows(args) -> np.ndarray:
 
 def device_points(X_train: np.ndarray, n_marks: int, grouped: bool):
     """The points to cluster as a device tensor: the marks (grouped) or the 10 x marks features."""
-    import torch
-    if not torch.cuda.is_available():
-        raise RuntimeError("expecto_amd.interpret_features needs a GPU (HIP) to cluster; there is no CPU path")
+    from . import _lib
+    torch = _lib.require_gpu("interpret_features", " to cluster")
     x = torch.from_numpy(X_train).cuda()
     return features_grouped(x, n_marks) if grouped else x.T
 

@@ -24,16 +24,13 @@ RANK_LDS_TILE = 2048      # values of the row it holds in LDS at a time
 MAX_BOOT = 4096
 
 
-def _device():
-    import torch
-    return torch.device("cuda", torch.cuda.current_device())
-
-
 def _to_device(a, dtype=None):
     import torch
+
+    from . import _lib
     t = a if torch.is_tensor(a) else torch.from_numpy(np.ascontiguousarray(a))
     if not t.is_cuda:
-        t = t.to(_device())
+        t = t.to(_lib.device_of())
     return t if dtype is None or t.dtype == dtype else t.to(dtype)
 
 
@@ -44,7 +41,6 @@ def rank2(x):
 
     from . import _lib
 
-    lib = _lib.load()
     t = _to_device(x)
     if t.dtype not in (torch.float32, torch.float64):
         raise TypeError(f"rank2: float32 or float64 values, not {t.dtype}")
@@ -57,11 +53,11 @@ def rank2(x):
     if n > MAX_ROWS:
         raise ValueError(f"rank2: n = {n} exceeds {MAX_ROWS}")
     out = torch.empty(P, n, dtype=torch.int32, device=rows.device)
-    fn = lib.expecto_rank2_f32 if t.dtype == torch.float32 else lib.expecto_rank2_f64
+    name = "expecto_rank2_f32" if t.dtype == torch.float32 else "expecto_rank2_f64"
     for p0 in range(0, P, 65535):                                   # the grid's y limit
         part = rows[p0:p0 + 65535]
-        _lib.check(fn(_lib.dptr(part), part.stride(0) if part.shape[0] > 1 else 0, n, int(part.shape[0]),
-                      _lib.dptr(out[p0:]), _lib.stream_ptr()), "rank2")
+        _lib.call(name, _lib.dptr(part), part.stride(0) if part.shape[0] > 1 else 0, n, int(part.shape[0]),
+                  _lib.dptr(out[p0:]), what="rank2")
     return out if t.dim() == 2 else out[0]
 
 
@@ -73,7 +69,6 @@ def model_metrics(pred, y) -> np.ndarray:
 
     from . import _lib
 
-    lib = _lib.load()
     p = _to_device(pred)
     if p.dim() != 2 or p.dtype != torch.float32:
         raise ValueError("model_metrics: pred must be float32 [P, n]")
@@ -88,8 +83,8 @@ def model_metrics(pred, y) -> np.ndarray:
     out = torch.empty(P, 3, dtype=torch.float64, device=p.device)
     if P:
         ra, rb = rank2(p), rank2(t)
-        _lib.check(lib.expecto_model_metrics(_lib.dptr(p), p.stride(0), _lib.dptr(t), 0 if shared else n, _lib.dptr(ra),
-                                             _lib.dptr(rb), n, P, _lib.dptr(out), _lib.stream_ptr()), "model_metrics")
+        _lib.call("expecto_model_metrics", _lib.dptr(p), p.stride(0), _lib.dptr(t), 0 if shared else n, _lib.dptr(ra),
+                  _lib.dptr(rb), n, P, _lib.dptr(out), what="model_metrics")
     return out.cpu().numpy()
 
 
@@ -101,7 +96,6 @@ def bootstrap_coef_stats(boot_weights, main_weights) -> dict:
 
     from . import _lib
 
-    lib = _lib.load()
     W = _to_device(boot_weights, torch.float64)
     w = _to_device(main_weights, torch.float64).contiguous()
     if W.dim() != 2 or (W.shape[1] > 1 and W.stride(1) != 1):
@@ -112,8 +106,7 @@ def bootstrap_coef_stats(boot_weights, main_weights) -> dict:
     if B < 2 or B > MAX_BOOT:
         raise ValueError(f"bootstrap_coef_stats: B = {B} outside [2, {MAX_BOOT}]")
     out = torch.empty(4, F, dtype=torch.float64, device=W.device)
-    _lib.check(lib.expecto_bootstrap_coef_stats(_lib.dptr(W), max(W.stride(0), F), B, F, _lib.dptr(w), _lib.dptr(out[0]),
-                                                _lib.dptr(out[1]), _lib.dptr(out[2]), _lib.dptr(out[3]),
-                                                _lib.stream_ptr()), "bootstrap_coef_stats")
+    _lib.call("expecto_bootstrap_coef_stats", _lib.dptr(W), max(W.stride(0), F), B, F, _lib.dptr(w), _lib.dptr(out[0]),
+              _lib.dptr(out[1]), _lib.dptr(out[2]), _lib.dptr(out[3]), what="bootstrap_coef_stats")
     h = out.cpu().numpy()
     return {"mean": h[0], "se": h[1], "z": h[2], "cv": h[3]}

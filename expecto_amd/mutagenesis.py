@@ -72,10 +72,10 @@ class ModelBank:
                                  f"10 x {keep.size} in one")
         self.models, self.keep_idx = models, keep
         self.names = list(names) if names is not None else [f"model{i}" for i in range(len(models))]
-        dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        dev = _lib.device_of(device)
         w = np.stack([m.weights[:, 0] for m in models], 1).astype(np.float32)
         init = np.array([np.float32(m.bias[0]) + np.float32(m.base_score) for m in models], np.float32)
-        self.w = torch.from_numpy(np.ascontiguousarray(w)).to(dev)
+        self.w = _lib.upload(w, dev)
         self.init = torch.from_numpy(init).to(dev)
         self.keep = torch.from_numpy(keep).to(dev)
 
@@ -114,9 +114,8 @@ def enumerate_region(dg, start: int, L: int):
     dev = dg.codes.device
     var_off = torch.empty(3 * L, dtype=torch.int64, device=dev)
     ref_code, alt_code, valid = (torch.empty(3 * L, dtype=torch.uint8, device=dev) for _ in range(3))
-    _lib.check(_lib.load().expecto_ism_variants(_lib.dptr(dg.codes), dg.codes.numel(), int(start), int(L),
-                                                _lib.dptr(var_off), _lib.dptr(ref_code), _lib.dptr(alt_code),
-                                                _lib.dptr(valid), _lib.stream_ptr()), "ism_variants")
+    _lib.call("expecto_ism_variants", _lib.dptr(dg.codes), dg.codes.numel(), int(start), int(L), _lib.dptr(var_off),
+              _lib.dptr(ref_code), _lib.dptr(alt_code), _lib.dptr(valid), what="ism_variants")
     return var_off, ref_code, alt_code, valid
 
 
@@ -166,11 +165,11 @@ def score_slots(y: torch.Tensor, dist: torch.Tensor, strand_plus: bool, shifts: 
                torch.empty((M, n // 3), dtype=torch.float32, device=dev),
                torch.empty((M, n), dtype=torch.float64, device=dev))
     alt_pred, ref_pred, sed = out
-    _lib.check(_lib.load().expecto_ism_score(
-        _lib.dptr(y[0, 0]), _lib.dptr(y[0, 1]), 2 * S * n, _lib.dptr(dist), int(bool(strand_plus)), _lib.dptr(shifts),
-        S, n, F, _lib.dptr(lut), int(lut.shape[1]), _lib.dptr(bank.keep), int(bank.keep.numel()), _lib.dptr(bank.w),
-        _lib.dptr(bank.init), M, _lib.dptr(valid), _lib.dptr(alt_pred), _lib.dptr(ref_pred), _lib.dptr(sed),
-        _lib.stream_ptr()), "ism_score")
+    _lib.call(
+        "expecto_ism_score", _lib.dptr(y[0, 0]), _lib.dptr(y[0, 1]), 2 * S * n, _lib.dptr(dist), int(bool(strand_plus)),
+        _lib.dptr(shifts), S, n, F, _lib.dptr(lut), int(lut.shape[1]), _lib.dptr(bank.keep), int(bank.keep.numel()),
+        _lib.dptr(bank.w), _lib.dptr(bank.init), M, _lib.dptr(valid), _lib.dptr(alt_pred), _lib.dptr(ref_pred),
+        _lib.dptr(sed), what="ism_score")
     return out
 
 
@@ -178,8 +177,8 @@ def summaries(sed_slots: torch.Tensor, valid: torch.Tensor):
     """(S(|sed|), S(sed)) per model over the slots in slot order: ``expecto_ism_summary``."""
     M, n = sed_slots.shape
     out = torch.empty((2, M), dtype=torch.float64, device=sed_slots.device)
-    _lib.check(_lib.load().expecto_ism_summary(_lib.dptr(sed_slots.contiguous()), _lib.dptr(valid), M, n,
-                                               _lib.dptr(out[0]), _lib.dptr(out[1]), _lib.stream_ptr()), "ism_summary")
+    _lib.call("expecto_ism_summary", _lib.dptr(sed_slots.contiguous()), _lib.dptr(valid), M, n, _lib.dptr(out[0]),
+              _lib.dptr(out[1]), what="ism_summary")
     return out[0], out[1]
 
 
@@ -241,28 +240,24 @@ def saturation(pipeline, models: ModelBank, chrom: str, tss: int, strand, upstre
     alt_pred = torch.empty((M, n), dtype=torch.float32, device=dev)
     ref_pred = torch.empty((M, L), dtype=torch.float32, device=dev)
     sed = torch.empty((M, n), dtype=torch.float64, device=dev)
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)] if timing is not None else None
-    fwd_ms = score_ms = 0.0
+    ms = {"forward_ms": 0.0, "score_ms": 0.0} if timing is not None else None     # summed over the batches
     for p0 in range(0, L, positions_per_batch):
         p1 = min(L, p0 + positions_per_batch)
         a, b = 3 * p0, 3 * p1
         whole = p0 == 0 and p1 == L
-        if ev:
-            ev[0].record()
+        timer = _lib.EventTimer(ms)
+        timer.mark()
         y = pipeline.predict(region_prep(pipeline, var_off[a:b], ref_code[a:b], alt_code[a:b], shifts))
-        if ev:
-            ev[1].record()
+        timer.mark()
         out = score_slots(y, dist_d[a:b], plus, shifts_d, lut, models, valid[a:b],
                           (alt_pred, ref_pred, sed) if whole else None)
         if not whole:                      # the kernel's rows are m * (b - a) + v
             alt_pred[:, a:b], ref_pred[:, p0:p1], sed[:, a:b] = out
-        if ev:
-            ev[2].record()
-            ev[2].synchronize()
-            fwd_ms += ev[0].elapsed_time(ev[1])
-            score_ms += ev[1].elapsed_time(ev[2])
+        timer.mark(sync=True)
+        timer.add("forward_ms", 0)
+        timer.add("score_ms", 1)
     if timing is not None:
-        timing.update(forward_ms=fwd_ms, score_ms=score_ms)
+        timing.update(ms)
     # [M, L, 4] in base-code order: the three alts scattered to their codes, +0.0 at the ref allele
     ok = valid.view(L, 3)[:, 0].bool()
     idx = torch.where(valid.bool(), alt_code, torch.arange(3, device=dev, dtype=torch.uint8).repeat(L)).long()
@@ -411,8 +406,7 @@ def run(args) -> list:
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    if not torch.cuda.is_available():
-        raise RuntimeError("expecto_amd.mutagenesis needs a GPU (HIP); there is no CPU path")
+    _lib.require_gpu("mutagenesis")
     return run(args)
 
 

@@ -30,7 +30,7 @@ import numpy as np
 import pandas as pd
 import torch
 
-from . import h5
+from . import _lib, h5
 from .features import fwd_rc_average, variant_features
 from .pipeline import shift_order
 from .xgblinear import GBLinear
@@ -239,7 +239,7 @@ def write_sorted(df: pd.DataFrame, out_dir: str, ext: str = "tsv") -> None:
 
 def run(args) -> pd.DataFrame:
     os.makedirs(args.out_dir, exist_ok=True)
-    dev = torch.device("cuda", torch.cuda.current_device())
+    dev = _lib.device_of()
     beluga_features_df = read_features_table(args.belugaFeatures)
     mask_args = mask_arguments(args)
     keep_mask = get_keep_mask(beluga_features_df, *mask_args)          # predict.py:61-62
@@ -258,8 +258,7 @@ def run(args) -> pd.DataFrame:
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    if not torch.cuda.is_available():
-        raise RuntimeError("expecto_amd.predict needs a GPU (HIP); there is no CPU path")
+    _lib.require_gpu("predict")
     return run(args)
 
 

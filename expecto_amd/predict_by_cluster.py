@@ -46,7 +46,7 @@ import numpy as np
 import pandas as pd
 import torch
 
-from . import predict
+from . import _lib, predict
 from .features import variant_contributions
 from .pipeline import shift_order
 from .xgblinear import GBLinear
@@ -131,7 +131,7 @@ def run(args) -> list:
     out_dirs = model_dirs(args.out_dir, model_files)
     for d in [args.out_dir] + out_dirs:
         os.makedirs(d, exist_ok=True)
-    dev = torch.device("cuda", torch.cuda.current_device())
+    dev = _lib.device_of()
     beluga_features_df = predict.read_features_table(args.belugaFeatures)
     mask_args = predict.mask_arguments(args)
     # predict_by_cluster_rsat.py:68 prints the filter messages here; predict_by_cluster.py has no such call
@@ -194,8 +194,7 @@ def run(args) -> list:
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
-    if not torch.cuda.is_available():
-        raise RuntimeError("expecto_amd.predict_by_cluster needs a GPU (HIP); there is no CPU path")
+    _lib.require_gpu("predict_by_cluster")
     return run(args)
 
 

@@ -223,36 +223,21 @@ def build_pssm(freqs, nsites, bg, pseudo: float = 0.1):
 
 # ---- device -----------------------------------------------------------------------------------
 
-def _need_gpu():
-    import torch
-    if not torch.cuda.is_available():
-        raise RuntimeError("expecto_amd.query_fimo_for_predictions needs a GPU (HIP); there is no CPU path")
-    return torch
-
-
-def _call(lib, name, *args):
-    from . import _lib
-    st = getattr(lib, name)(*args, _lib.stream_ptr())
-    if st != 0:
-        raise RuntimeError(f"{name} failed (status {st}): {lib.expecto_last_error().decode()}")
-
-
 def pvalue_tables(motifs: Motifs, bg, device=None) -> Tables:
     """The motifs on the device with their score-to-p-value tables (one ``expecto_pwm_pvalues`` call)."""
-    torch = _need_gpu()
     from . import _lib
-    lib = _lib.load()
+    torch = _lib.require_gpu("query_fimo_for_predictions")
     bg = np.ascontiguousarray(_checked_bg(bg)[TO_CODE_ORDER])
-    dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+    dev = _lib.device_of(device)
     M, total = len(motifs), int(motifs.col_ptr[-1])
     with torch.cuda.device(dev):
         pssm = torch.from_numpy(motifs.pssm).to(dev)
         col_ptr = torch.from_numpy(motifs.col_ptr).to(dev)
         tables = torch.empty(RANGE * total + M, dtype=torch.float64, device=dev)
         pv_ptr = torch.zeros(M + 1, dtype=torch.int64, device=dev)
-        _call(lib, "expecto_pwm_pvalues", pssm.data_ptr() if total else None, motifs.col_ptr.ctypes.data,
-              col_ptr.data_ptr(), M, bg.ctypes.data, tables.data_ptr() if M else None, pv_ptr.data_ptr(),
-              int(tables.numel()))
+        _lib.call("expecto_pwm_pvalues", pssm.data_ptr() if total else None, motifs.col_ptr.ctypes.data,
+                  col_ptr.data_ptr(), M, bg.ctypes.data, tables.data_ptr() if M else None, pv_ptr.data_ptr(),
+                  int(tables.numel()))
     return Tables(pssm, col_ptr, tables, pv_ptr)
 
 
@@ -261,12 +246,11 @@ def scan(codes, overlap, motifs: Motifs, tables: Tables):
     tensors [S, M] (one ``expecto_pwm_scan`` call).  codes: uint8 [S, L] base codes (a device tensor with
     contiguous rows is used in place; a host array is uploaded); overlap: one position for all sequences or
     int32 [S], -1 for "any window"."""
-    torch = _need_gpu()
     from . import _lib
-    lib = _lib.load()
+    torch = _lib.require_gpu("query_fimo_for_predictions")
     dev = tables.tables.device
     if not torch.is_tensor(codes):
-        codes = torch.from_numpy(np.ascontiguousarray(codes, np.uint8)).to(dev)
+        codes = _lib.upload(np.asarray(codes, np.uint8), dev)
     if codes.dtype != torch.uint8 or codes.dim() != 2 or not codes.is_cuda or (codes.shape[1] > 1 and codes.stride(1) != 1):
         raise ValueError("codes must be uint8 [S, L] on the device with contiguous rows")
     S, L = int(codes.shape[0]), int(codes.shape[1])
@@ -276,7 +260,7 @@ def scan(codes, overlap, motifs: Motifs, tables: Tables):
     if np.ndim(overlap) == 0 and not torch.is_tensor(overlap):
         overlap = torch.full((S,), int(overlap), dtype=torch.int32, device=dev)
     elif not torch.is_tensor(overlap):
-        overlap = torch.from_numpy(np.ascontiguousarray(overlap, np.int32)).to(dev)
+        overlap = _lib.upload(np.asarray(overlap, np.int32), dev)
     if overlap.dtype != torch.int32 or overlap.shape != (S,) or not overlap.is_contiguous():
         raise ValueError("overlap must be one position or int32 [S]")
     M = len(motifs)
@@ -286,10 +270,10 @@ def scan(codes, overlap, motifs: Motifs, tables: Tables):
         strand = torch.empty((S, M), dtype=torch.uint8, device=dev)
         pvalue = torch.empty((S, M), dtype=torch.float64, device=dev)
         if S and M:
-            _call(lib, "expecto_pwm_scan", codes.data_ptr(), S, L, ld, overlap.data_ptr(), tables.pssm.data_ptr(),
-                  motifs.col_ptr.ctypes.data, tables.col_ptr.data_ptr(), M, tables.tables.data_ptr(),
-                  tables.pv_ptr.data_ptr(), int(tables.tables.numel()), score.data_ptr(), start.data_ptr(),
-                  strand.data_ptr(), pvalue.data_ptr())
+            _lib.call("expecto_pwm_scan", codes.data_ptr(), S, L, ld, overlap.data_ptr(), tables.pssm.data_ptr(),
+                      motifs.col_ptr.ctypes.data, tables.col_ptr.data_ptr(), M, tables.tables.data_ptr(),
+                      tables.pv_ptr.data_ptr(), int(tables.tables.numel()), score.data_ptr(), start.data_ptr(),
+                      strand.data_ptr(), pvalue.data_ptr())
     return score, start, strand, pvalue
 
 
@@ -443,8 +427,9 @@ def run(args):
     """One CLI run; returns the DataFrame of ``fimo_filtered.tsv`` (exact p-values and scores)."""
     import pandas as pd
 
+    from . import _lib
     from .genome import open_genome
-    torch = _need_gpu()
+    torch = _lib.require_gpu("query_fimo_for_predictions")
     if args.seq_batch < 1:
         raise ValueError("--seq-batch must be at least 1")
     os.makedirs(args.out_dir, exist_ok=True)

@@ -166,13 +166,10 @@ class _Device:
     """The device side of both passes: the library, the kept marks and the buffers a chunk needs."""
 
     def __init__(self, keep, device):
-        import torch
-
         from . import _lib
-        if not torch.cuda.is_available():
-            raise RuntimeError("expecto_amd.svd needs a GPU (HIP); there is no CPU path")
+        torch = _lib.require_gpu("svd")
         self.torch, self._lib, self.lib = torch, _lib, _lib.load()
-        self.dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self.dev = _lib.device_of(device)
         self.m = int(keep.size)
         with torch.cuda.device(self.dev):
             self.keep = torch.from_numpy(keep.astype(np.int32)).to(self.dev)
@@ -181,16 +178,14 @@ class _Device:
 
     def call(self, name, *args):
         with self.torch.cuda.device(self.dev):
-            st = getattr(self.lib, name)(*args, self._lib.stream_ptr())
-        if st != 0:
-            raise RuntimeError(f"{name} failed (status {st}): {self.lib.expecto_last_error().decode()}")
+            self._lib.call(name, *args)
 
     def upload(self, host):
-        return self.torch.from_numpy(host).to(self.dev)
+        return self._lib.upload(host, self.dev)
 
     def workspace(self, nbytes):
         if self.ws is None or self.ws.numel() * 8 < nbytes:
-            self.ws = self.torch.empty((nbytes + 7) // 8, dtype=self.torch.float64, device=self.dev)
+            self.ws = self._lib.workspace(nbytes, self.dev)
         return self.ws
 
     def stats(self, D, idf):

@@ -341,11 +341,10 @@ def run(args, model_dir=None) -> list:
 
 
 def main(argv=None):
-    import torch
+    from . import _lib
 
     args = build_parser(cv=True).parse_args(argv)
-    if not torch.cuda.is_available():
-        raise RuntimeError("expecto_amd.train needs a GPU (HIP); there is no CPU path")
+    _lib.require_gpu("train")
     return run(args)
 
 

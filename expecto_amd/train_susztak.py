@@ -41,11 +41,10 @@ def run(args) -> list:
 
 
 def main(argv=None):
-    import torch
+    from . import _lib
 
     args = build_parser().parse_args(argv)
-    if not torch.cuda.is_available():
-        raise RuntimeError("expecto_amd.train_susztak needs a GPU (HIP); there is no CPU path")
+    _lib.require_gpu("train_susztak")
     return run(args)
 
 

@@ -201,7 +201,6 @@ class GBLinear:
 
         from . import _lib
 
-        lib = _lib.load()
         if X.dtype != torch.float64 or X.dim() != 2 or X.stride(1) != 1:
             raise RuntimeError("gblinear predict: X must be a float64 [n, ld] tensor with contiguous rows")
         n = X.shape[0]
@@ -211,13 +210,12 @@ class GBLinear:
             cols = torch.arange(self.num_feature, dtype=torch.int32, device=X.device)
         if cols.numel() != self.num_feature:
             raise RuntimeError(f"model has {self.num_feature} features, {cols.numel()} columns given")
-        w = torch.from_numpy(np.ascontiguousarray(self.weights[:, group])).to(X.device)
+        w = _lib.upload(self.weights[:, group], X.device)
         init = float(np.float32(self.bias[group]) + np.float32(self.base_score))   # bias + base, in f32
         if out is None:
             out = torch.empty(n, dtype=torch.float32, device=X.device)
-        _lib.check(lib.expecto_gblinear_predict(_lib.dptr(X), n, X.stride(0), _lib.dptr(cols.contiguous()),
-                                                self.num_feature, _lib.dptr(w), float(init), _lib.dptr(out),
-                                                _lib.stream_ptr()), "gblinear_predict")
+        _lib.call("expecto_gblinear_predict", _lib.dptr(X), n, X.stride(0), _lib.dptr(cols.contiguous()),
+                  self.num_feature, _lib.dptr(w), float(init), _lib.dptr(out), what="gblinear_predict")
         return out
 
 
@@ -230,12 +228,13 @@ class ColMatrix:
     def __init__(self, X, device=None, chunk: int = 1024):
         import torch
 
+        from . import _lib
+
         if isinstance(X, np.ndarray):
             X = torch.from_numpy(X)
         if X.dim() != 2:
             raise RuntimeError("gblinear train: X must be [n, F]")
-        dev = torch.device(device) if device is not None else (
-            X.device if X.is_cuda else torch.device("cuda", torch.cuda.current_device()))
+        dev = _lib.device_of(X.device if device is None and X.is_cuda else device)
         self.n, self.F = int(X.shape[0]), int(X.shape[1])
         self.ld = max(64, (self.n + 63) // 64 * 64)
         self.data = torch.zeros(max(self.F, 1), self.ld, dtype=torch.float32, device=dev)
@@ -267,11 +266,11 @@ def _batch(parts):
     return sizes.pop() if sizes else None
 
 
-def _rmse(lib, pred, y, h, n, B, out):
+def _rmse(pred, y, h, n, B, out):
     from . import _lib
 
-    _lib.check(lib.expecto_gblinear_rmse(_lib.dptr(pred), _lib.dptr(y[0]), y[2], _lib.dptr(h[0]) if h else None,
-                                         h[2] if h else 0, n, B, _lib.dptr(out), _lib.stream_ptr()), "gblinear_rmse")
+    _lib.call("expecto_gblinear_rmse", _lib.dptr(pred), _lib.dptr(y[0]), y[2], _lib.dptr(h[0]) if h else None,
+              h[2] if h else 0, n, B, _lib.dptr(out), what="gblinear_rmse")
 
 
 def predict_cols(X, models):
@@ -279,9 +278,6 @@ def predict_cols(X, models):
     ``[B, n]`` device tensor, by the prediction rule above (``expecto_gblinear_predict_cols``)."""
     import torch
 
-    from . import _lib
-
-    lib = _lib.load()
     single = isinstance(models, GBLinear)
     ms = [models] if single else list(models)
     if any(m.num_feature != X.F or m.groups != 1 for m in ms):
@@ -292,16 +288,15 @@ def predict_cols(X, models):
         np.zeros((0, X.F + 1), np.float32)
     out = torch.empty(len(ms), X.n, dtype=torch.float32, device=X.device)
     if ms:
-        _predict_cols(lib, X, torch.from_numpy(w).to(X.device), float(ms[0].base_score), out)
+        _predict_cols(X, torch.from_numpy(w).to(X.device), float(ms[0].base_score), out)
     return out[0] if single else out
 
 
-def _predict_cols(lib, X, w, base_score, out):
+def _predict_cols(X, w, base_score, out):
     from . import _lib
 
-    _lib.check(lib.expecto_gblinear_predict_cols(_lib.dptr(X.data), X.ld, X.n, X.F, int(w.shape[0]), _lib.dptr(w),
-                                                 float(base_score), _lib.dptr(out), _lib.stream_ptr()),
-               "gblinear_predict_cols")
+    _lib.call("expecto_gblinear_predict_cols", _lib.dptr(X.data), X.ld, X.n, X.F, int(w.shape[0]), _lib.dptr(w),
+              float(base_score), _lib.dptr(out), what="gblinear_predict_cols")
 
 
 _HYPER = ("eta", "lambda_", "alpha", "lambda_bias")
@@ -334,7 +329,7 @@ def _part(p, c0, c1):
     return p if p is None or p[1] is None else (p[0][c0:c1], c1 - c0, p[2])
 
 
-def _round(lib, Xc, y, h, w, sh, first, hyper, base, pred):
+def _round(Xc, y, h, w, sh, first, hyper, base, pred):
     """One round of the models of ``w``: ``hyper`` is a tuple of four floats for all of them
     (``expecto_gblinear_train_round``) or a float64 ``[b, 4]`` device tensor, a row per model
     (``expecto_gblinear_train_round_hp``)."""
@@ -342,15 +337,14 @@ def _round(lib, Xc, y, h, w, sh, first, hyper, base, pred):
 
     head = (_lib.dptr(Xc.data), Xc.ld, Xc.n, Xc.F, int(w.shape[0]), _lib.dptr(y[0]), y[2],
             _lib.dptr(h[0]) if h else None, h[2] if h else 0, _lib.dptr(w), _lib.dptr(sh), int(first))
-    tail = (base, _lib.dptr(pred) if pred is not None else None, _lib.stream_ptr())
+    tail = (base, _lib.dptr(pred) if pred is not None else None)
     if isinstance(hyper, tuple):
-        st = lib.expecto_gblinear_train_round(*head, *hyper, *tail)
+        _lib.call("expecto_gblinear_train_round", *head, *hyper, *tail, what="gblinear_train_round")
     else:
-        st = lib.expecto_gblinear_train_round_hp(*head, _lib.dptr(hyper), *tail)
-    _lib.check(st, "gblinear_train_round")
+        _lib.call("expecto_gblinear_train_round_hp", *head, _lib.dptr(hyper), *tail, what="gblinear_train_round")
 
 
-def _fit(lib, Xc, y, h, hyper, w, num_round, base, train_pred, after_round=None):
+def _fit(Xc, y, h, hyper, w, num_round, base, train_pred, after_round=None):
     """``num_round`` rounds of the models of ``w`` (in place).  ``train_pred(r, pred)`` is called with
     the train predictions after round r (0-based): for every round but the last they are what the
     next round's own predict pass writes, so only the last costs a pass over X.
@@ -361,13 +355,13 @@ def _fit(lib, Xc, y, h, hyper, w, num_round, base, train_pred, after_round=None)
     sh = torch.empty(b, max(Xc.F, 1), dtype=torch.float64, device=w.device)
     pred = torch.empty(b, n, dtype=torch.float32, device=w.device)
     for r in range(num_round):
-        _round(lib, Xc, y, h, w, sh, r == 0, hyper, base, pred if r > 0 else None)
+        _round(Xc, y, h, w, sh, r == 0, hyper, base, pred if r > 0 else None)
         if r > 0 and n > 0:
             train_pred(r - 1, pred)
         if after_round is not None:
             after_round(r)
     if num_round > 0 and n > 0:
-        _predict_cols(lib, Xc, w, base, pred)
+        _predict_cols(Xc, w, base, pred)
         train_pred(num_round - 1, pred)
 
 
@@ -392,9 +386,6 @@ def train(X, y, weight=None, *, num_round=100, eta=0.01, lambda_=100.0, alpha=0.
         raise ValueError("gblinear train: chunk must be at least 1")
     import torch
 
-    from . import _lib
-
-    lib = _lib.load()
     Xc = X if isinstance(X, ColMatrix) else ColMatrix(X)
     dev, n, F = Xc.device, Xc.n, Xc.F
     yt = _rows(y, n, "y", dev)
@@ -421,15 +412,15 @@ def train(X, y, weight=None, *, num_round=100, eta=0.01, lambda_=100.0, alpha=0.
                for Xe, ye, he in ev]
 
         def train_pred(r, pred):
-            _rmse(lib, pred, yc, hc, n, c1 - c0, hist[r, 0, c0:c1])
+            _rmse(pred, yc, hc, n, c1 - c0, hist[r, 0, c0:c1])
 
         def after_round(r):
             for k, (Xe, ye, he, ep) in enumerate(evc):
                 if Xe.n > 0:
-                    _predict_cols(lib, Xe, wc, base, ep)
-                    _rmse(lib, ep, ye, he, Xe.n, c1 - c0, hist[r, 1 + k, c0:c1])
+                    _predict_cols(Xe, wc, base, ep)
+                    _rmse(ep, ye, he, Xe.n, c1 - c0, hist[r, 1 + k, c0:c1])
 
-        _fit(lib, Xc, yc, hc, hyper if Bh is None else hyper_dev[c0:c1], wc, num_round, base, train_pred, after_round)
+        _fit(Xc, yc, hc, hyper if Bh is None else hyper_dev[c0:c1], wc, num_round, base, train_pred, after_round)
     wh = w.cpu().numpy()
     history = hist[:num_round].permute(2, 0, 1).contiguous().cpu().numpy()
     models = [GBLinear(wh[m, :F].reshape(F, 1).copy(), wh[m, F:].copy(), base) for m in range(B)]
@@ -602,9 +593,6 @@ def cv(X, y, fold, grid, *, weight=None, num_round=100, eta=0.01, lambda_bias=0.
 
     import torch
 
-    from . import _lib
-
-    lib = _lib.load()
     Xc = X if Xc_given else ColMatrix(X)
     dev = Xc.device
     Y, W = torch.from_numpy(yh).to(dev), torch.from_numpy(np.ascontiguousarray(wt)).to(dev)
@@ -626,10 +614,10 @@ def cv(X, y, fold, grid, *, weight=None, num_round=100, eta=0.01, lambda_bias=0.
         vc = ((W[t_of] * held).contiguous(), b, n)
 
         def train_pred(r, pred):
-            _rmse(lib, pred, yc, hc, n, b, out[0, r, c0:c1])
-            _rmse(lib, pred, yc, vc, n, b, out[1, r, c0:c1])
+            _rmse(pred, yc, hc, n, b, out[0, r, c0:c1])
+            _rmse(pred, yc, vc, n, b, out[1, r, c0:c1])
 
-        _fit(lib, Xc, yc, hc, hyper_dev[c0:c1], torch.zeros(b, Xc.F + 1, dtype=torch.float32, device=dev), num_round,
+        _fit(Xc, yc, hc, hyper_dev[c0:c1], torch.zeros(b, Xc.F + 1, dtype=torch.float32, device=dev), num_round,
              base, train_pred)
     res = out.permute(0, 2, 1).contiguous().cpu().numpy().reshape(2, T, G, K, num_round)
     score, se, best_g, best_round = cv_select(res[1], rule)

@@ -356,8 +356,13 @@ def test_permutations_leave_the_reference_problems(lib, caf, tmp_path, monkeypat
         single = caf.enrichment(inp.contrib, inp.sets, inp.matches, caf.permutation_batch(inp, [draws[j]]), 20, 6,
                                 n_motifs=len(inp.motifs))
         assert_bits(single.pval, null[:, j], f"null row {j}")
+    timings = {"sf_ms": 1e9}
     both = caf.enrichment(torch.from_numpy(inp.contrib).cuda(), caf.bitsets(inp.sets, len(inp.motifs)),
-                          caf.csr(inp.matches), caf.permutation_batch(inp, draws[1:]), 20, 6, n_motifs=len(inp.motifs))
+                          caf.csr(inp.matches), caf.permutation_batch(inp, draws[1:]), 20, 6, n_motifs=len(inp.motifs),
+                          timings=timings)
     assert_bits(both.pval[0::2], null[0, 1:], "device tensor, clusters")
     assert_bits(both.pval[1::2], null[1, 1:], "device tensor, variants")
+    assert set(timings) == {"upload_ms", "enrich_ms", "sf_ms"}
+    assert all(isinstance(v, float) and np.isfinite(v) and v >= 0 for v in timings.values())
+    assert timings["sf_ms"] >= 1e9                                     # these keys accumulate over calls
     assert os.path.exists(tmp_path / "b" / "permutation_null.tsv")

@@ -310,7 +310,10 @@ def test_cli_writes_matrices_summary_and_vcf(world, capsys):
              "--belugaFeatures", feats_path, "--no_pol2", "--upstream", "3", "--downstream", "3", "--maxshift", "200",
              "-o", str(out), "--vcf-out", "--genome", str(d / "hg19.fa"), "--synthetic-weights", "0", "--max-batch", "300"])
     assert sorted(os.listdir(out)) == ["ENSGT0001.ism.h5", "ENSGT0001.vcf", "summary.tsv"]
-    res = mg.saturation(world["pipe"], mg.ModelBank(models, keep), "chr1", tss, "+", 3, 3, 200)
+    timing = {}
+    res = mg.saturation(world["pipe"], mg.ModelBank(models, keep), "chr1", tss, "+", 3, 3, 200, timing=timing)
+    assert set(timing) == {"forward_ms", "score_ms"}
+    assert all(isinstance(v, float) and np.isfinite(v) and v >= 0 for v in timing.values())
     vp, dr = (x.cpu().numpy() for x in res.summaries())
     tab = pd.read_csv(out / "summary.tsv", sep="\t", float_precision="round_trip")
     assert list(tab.columns) == ["gene", "model", "variation_potential", "directionality"]

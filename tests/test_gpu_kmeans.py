@@ -377,7 +377,10 @@ def test_sweep_equals_single_fits():
     from expecto_amd.cluster_and_viz import kmeans, kmeans_sweep
     X = kmeans_ref.INPUTS["gauss2002"]()
     ks = [197, 2, 30]
-    swept = kmeans_sweep(X, ks, seed=0)
+    timings = {}
+    swept = kmeans_sweep(X, ks, seed=0, timings=timings)
+    assert set(timings) == {"seeding_ms", "lloyd_ms"}
+    assert all(isinstance(v, float) and np.isfinite(v) and v >= 0 for v in timings.values())
     for k, r in zip(ks, swept):
         if k != 2:
             assert_matches_sklearn(r, kmeans_ref.case_name("gauss2002", k, 1, 0), X.shape[0])

@@ -60,7 +60,7 @@ def device(shapes, reps):
         t1 = time.perf_counter()
         host = cond.cpu().numpy()
         t2 = time.perf_counter()
-        interpret_features._link(lib, host, n)
+        interpret_features._link(host, n)
         t3 = time.perf_counter()
         print(json.dumps({"what": "ward_tree stages", "shape": name, "kernel_s": t1 - t0, "d2h_s": t2 - t1,
                           "linkage_s": t3 - t2, "total_s": t3 - t0}), flush=True)
