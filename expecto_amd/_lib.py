@@ -154,6 +154,10 @@ SIGNATURES = {
                                          ctypes.c_int, ctypes.c_int, c_vp, ctypes.c_int, c_vp, ctypes.c_int, c_vp, c_vp,
                                          ctypes.c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "expecto_ism_summary": (ctypes.c_int, [c_vp, c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp, c_vp]),
+    "expecto_ecdf_tail_counts": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, c_vp, c_vp, ctypes.c_int, c_vp,
+                                                ctypes.c_longlong, ctypes.c_int, c_vp, c_vp]),
+    "expecto_ecdf_summary": (ctypes.c_int, [c_vp, ctypes.c_int, ctypes.c_int, c_vp, ctypes.c_int, ctypes.c_int, c_vp,
+                                            c_vp, c_vp, c_vp, c_vp]),
     "expecto_last_error": (ctypes.c_char_p, []),
     "expecto_version": (ctypes.c_char_p, []),
 }

@@ -7,7 +7,7 @@ import subprocess
 import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCES = [os.path.join(HERE, "csrc", f) for f in ("beluga.hip", "reduce.hip", "train.hip", "cluster.hip", "silhouette.hip", "svd.hip", "kmeans.hip", "tsne.hip", "enrich.hip", "pwm.hip", "metrics.hip", "motif_cluster.hip", "louvain.hip", "ism.hip")]
+SOURCES = [os.path.join(HERE, "csrc", f) for f in ("beluga.hip", "reduce.hip", "train.hip", "cluster.hip", "silhouette.hip", "svd.hip", "kmeans.hip", "tsne.hip", "enrich.hip", "pwm.hip", "metrics.hip", "motif_cluster.hip", "louvain.hip", "ism.hip", "ecdf.hip")]
 OUT = os.path.join(HERE, "libexpecto_hip.so")
 ARCH = os.environ.get("EXPECTO_OFFLOAD_ARCH", "gfx950")
 

@@ -73,6 +73,8 @@
  *                                  coefficient of variation (plot_bootstrapped_coefficients.py:56,64,75)
  *   expecto_ism_variants / _score  no reference script: saturation mutagenesis, i.e. every SNV of a region
  *   expecto_ism_summary            through chromatin.py, make_closest_genes_file.py and predict.py per model
+ *   expecto_ecdf_tail_counts       no reference script: e-values of effects against a background variant set,
+ *   expecto_ecdf_summary           this project's definitions
  *   expecto_beluga_destroy         (model teardown)
  */
 #ifndef EXPECTO_HIP_H
@@ -954,6 +956,46 @@ int expecto_ism_score(const float* y_ref, const float* y_alt, long long strand_s
                       const uint8_t* valid, float* alt_pred, float* ref_pred, double* sed, void* stream);
 int expecto_ism_summary(const double* sed, const uint8_t* valid, int n_models, int n, double* potential,
                         double* direction, void* stream);
+
+/* Empirical significance of effects against a background (e-values).  These definitions are this project's:
+ * the reference has no script for them and no published table is reproduced.  All pointers are DEVICE memory
+ * unless noted; a refused call (EXPECTO_EINVAL) launches and writes nothing.
+ *
+ * Inputs.  bg float32 [C, B]: per mark c the B background effect magnitudes sorted ascending, no NaN,
+ * 1 <= B <= 2^31 - 2.  x float32 [n, >= max(cols) + 1] with row stride x_stride (elements).  cols[nc]: ascending
+ * mark indices in 0..C-1, 1 <= nc <= C, given twice: cols_host (HOST memory) is checked -- ascending, in range,
+ * x_stride >= cols_host[nc-1] + 1 -- before any launch, cols is the same list on the device and the caller's
+ * duty to keep equal.  With a = |x[v, cols[j]]|:
+ *   ge[v, j]     = #{b : bg[cols[j], b] >= a}, int32 [n, nc] contiguous.  Exact; ties count; a = +inf counts the
+ *                  background's infinities; a NaN query gives -1.
+ *   e[v, j]      = (ge + 1) / (B + 1) in float64 (the add-one form of permutation_null.tsv);
+ *   nlog[v, j]   = lut[ge[v, j]], lut[k] = -log10((k + 1) / (B + 1)) a float64 table of B + 1 entries that the
+ *                  HOST computes and uploads (as the exp table of expecto_variant_reduce_lut: the device log
+ *                  differs in the last ulp);
+ *   mean_nlog[v] = S(nlog[v, 0..nc-1]) / nc, S the fixed order of expecto_variant_contrib;
+ *   max_nlog[v]  = the largest nlog[v, j];
+ *   top[v]       = the lowest j whose ge[v, j] is the row's smallest;
+ *   n_sig[v]     = #{j : ge[v, j] + 1 <= k_alpha}, k_alpha = floor(alpha * (B + 1)) an integer the HOST computes,
+ *                  0 <= k_alpha <= B + 1.
+ * A variant with a NaN query (a -1 in its ge row) gets NaN in mean_nlog and max_nlog and -1 in top and n_sig.
+ * No atomics: every output depends on its own inputs alone, not on n or the grid.
+ *
+ * expecto_ecdf_tail_counts: a two-level lower bound.  A workgroup of 16 waves owns EXPECTO_ECDF_TILE_COLS = 16
+ * columns, one per wave, and keeps of each EXPECTO_ECDF_SPLITTERS = 2048 splitters (every ceil(B / 2048)-th
+ * value; the whole column where B <= 2048) in 128 KiB of LDS; |x| passes through a [16][257]-word LDS tile
+ * (16 KiB) that transposes 256 variants so that lanes are variants, four per lane side by side.  The first
+ * 11 halving steps read LDS, the remaining bit_length(ceil(B / 2048) - 1) read the column (6 at B = 10^5).
+ * Column tiles are dealt to the 8 workgroup groups of the XCDs, so the workgroups that share an L2 search the
+ * same 16 columns while the variants stream past.  n = 0 succeeds without a launch.
+ *
+ * expecto_ecdf_summary: one wave per variant reads the ge row (every entry -1 or 0..B, as tail_counts writes
+ * them), gathers lut and reduces. */
+#define EXPECTO_ECDF_SPLITTERS 2048
+#define EXPECTO_ECDF_TILE_COLS 16
+int expecto_ecdf_tail_counts(const float* bg, int B, int C, const int* cols_host, const int* cols, int nc,
+                             const float* x, long long x_stride, int n, int* ge, void* stream);
+int expecto_ecdf_summary(const int* ge, int n, int nc, const double* lut, int B, int k_alpha, double* mean_nlog,
+                         double* max_nlog, int* top, int* n_sig, void* stream);
 
 const char* expecto_last_error(void);
 const char* expecto_version(void);
